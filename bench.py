@@ -53,6 +53,7 @@ PMC_PROFILE = "r06_pmc_traffic.json"     # profiles/<this>: rocprofv3 --pmc FETC
 
 T_FRAMES, STEPS, CFG, LAT = 18, 25, 4.5, 64
 P = "v3d_amd.sgm.modules.diffusionmodules."
+DUMP_BYTES = 64 * 10 ** 6      # --dump-outputs: size limit of all .npy files together (headers included)
 
 
 def csrc_digest() -> str:
@@ -244,6 +245,26 @@ class _Timed:
             a[2] += by
             a[3] += 1
         return fam
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as <path>/<name>.npy in float32.  If they would exceed DUMP_BYTES together, each one is written as
+    <name>_sample.npy instead: the elements at a fixed seeded choice of flat positions (the same positions for the same shape), so the
+    files of two builds still compare element for element.  Returns {file: shape} for the result line."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    header = 4096                   # generous bound of one .npy header
+    total = sum(a.numel() * 4 + header for a in arrays.values())
+    written = {}
+    for name, a in arrays.items():
+        a = a.detach().float().cpu().contiguous()
+        if total > DUMP_BYTES:
+            n = (a.numel() * 4 + header) * DUMP_BYTES // total // 4 - header // 4
+            idx = torch.randperm(a.numel(), generator=torch.Generator().manual_seed(0))[:n].sort().values
+            a, name = a.flatten()[idx], name + "_sample"
+        np.save(os.path.join(path, name + ".npy"), a.numpy())
+        written[name + ".npy"] = list(a.shape)
+    return written
 
 
 def _safe(fn):
@@ -567,7 +588,12 @@ def main():
     ap.add_argument("--graph", action="store_true",
                     help="replay captured HIP graphs of the network evaluation / decode instead of launching from Python "
                          "(measured 9.59 vs 9.62 frames/s: ROCm 7.2 graph replay does not close the launch gaps, so it is off by default)")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (the decoded frames, rank 0) to DIR/<name>.npy in float32, "
+                         "at most 64 MB in all (a larger output becomes a fixed seeded sample of its elements, DIR/<name>_sample.npy)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     rank = int(os.environ.get("RANK", 0))
     local_rank = int(os.environ.get("LOCAL_RANK", 0))
@@ -639,6 +665,7 @@ def main():
     assert out.shape == (B_IN * T_FR, 3, LH * 8, LW * 8) and torch.isfinite(out).all()
     from v3d_amd.ops import get_ops as _get_ops
     _get_ops().check_health()                 # a stream-K hand-off that gave up would have produced a wrong tile silently: fail the run instead
+    dumped = dump_outputs(args.dump_outputs, {"frames": out}) if args.dump_outputs and rank == 0 else None
 
     result = None
     samples = args.steps * (1 if shard_mode else world)
@@ -669,6 +696,8 @@ def main():
             "dtype": "bf16 (fp8 e4m3 spatial attention)" if args.fp8 else "bf16", "data": "synthetic",
             "config": {"workload": wl, "frames": T_FR, "inputs_per_step": B_IN, "edm_steps": E_STEPS, "latent": [B_IN * T_FR, 4, LH, LW], "parallelism": par},
         }
+        if dumped is not None:
+            result["dumped_outputs"] = {"dir": args.dump_outputs, "files": dumped}
         if world > 1:
             try:
                 ver = ".".join(str(v) for v in torch.cuda.nccl.version())

@@ -39,6 +39,28 @@ def test_committed_bench_lines_keep_the_contract():
         assert c["kind"] in ("reference", "port") and c["unit"] == d["unit"]
 
 
+def test_dump_outputs_whole_or_seeded_sample_within_the_limit(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float32 .npy files, whole when they fit DUMP_BYTES, else the same seeded positions on every call."""
+    import sys
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    x = torch.randn(2, 3, 8, 8, dtype=torch.bfloat16)
+    assert bench.dump_outputs(str(tmp_path / "whole"), {"frames": x}) == {"frames.npy": [2, 3, 8, 8]}
+    got = np.load(tmp_path / "whole" / "frames.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, x.float().numpy())
+    monkeypatch.setattr(bench, "DUMP_BYTES", 3 * 4096)
+    big = torch.randn(4, 3, 64, 64)
+    for d in ("s1", "s2"):
+        files = bench.dump_outputs(str(tmp_path / d), {"frames": big})
+        assert list(files) == ["frames_sample.npy"]
+        assert sum(os.path.getsize(tmp_path / d / f) for f in files) <= bench.DUMP_BYTES
+    a, b = np.load(tmp_path / "s1" / "frames_sample.npy"), np.load(tmp_path / "s2" / "frames_sample.npy")
+    assert a.dtype == np.float32 and 0 < a.size < big.numel() and np.array_equal(a, b)
+    assert np.isin(a, big.flatten().numpy()).all()
+
+
 def test_pmc_profile_bench_reads_is_committed_and_not_older_than_the_kernels():
     """roofline.traffic comes from the rocprofv3 PMC passes committed under profiles/ (counters cannot be collected inside bench.py).
     The profile records the content hash of v3d_amd/csrc it was taken on: a kernel change after the last profile run fails here until

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define V3D_ABI_VERSION 5
+#define V3D_ABI_VERSION 6
 
 typedef void* v3d_stream_t; /* hipStream_t */
 
@@ -329,6 +329,17 @@ int v3d_nchw_to_nhwc_bf16(const float* x, float scale, void* out_bf16, int64_t n
  * of frame 0 (a leading halo frame under frame sharding) */
 int v3d_tmix_small(const float* x, int64_t ld, const float* w, const float* b, float* out, int64_t B, int32_t T,
                    int64_t S, int32_t Cc, int32_t tmin, int32_t tmax, int64_t row0, v3d_stream_t stream);
+/* Ancestral-sampler noise (AncestralSampler.ancestral_step / noise_sampler, sampling.py:136-212,240-360 (EDM-churn's randn_like is not
+ * moved here)): out[i] = (x ? x[i] : 0) + scale * N(seed, call, g(i)), N = Philox4x32-10 + Box-Muller, fully specified in csrc/noise.hip.
+ * x / out [B * T_local][row_elems] fp32 (out may be x), row_elems % 4 == 0, 16-byte aligned; g(i) = the element's flat index in the
+ * unsharded [B * T_global][row_elems] tensor, local row b T_local + t = global row b T_global + t0 + t: frame shards draw the same numbers
+ * as the unsharded run, bit for bit. */
+int v3d_randn_add(const float* x, float scale, uint64_t seed, uint32_t call, float* out, int64_t B, int64_t T_local, int64_t T_global,
+                  int64_t t0, int64_t row_elems, v3d_stream_t stream);
+/* Small linear combination of the DPM++ 2M / linear-multistep updates (sampling.py:136-212,240-360; to_d / linear_multistep_coeff:
+ * sampling_utils.py:7-36): out[i] = sum_k coef[k] * src[k][i], 1 <= nterms <= 6, fp32, terms added in order k = 0, 1, ...
+ * src (array of nterms device pointers) and coef are HOST pointers; out may alias any source. */
+int v3d_lincomb_f32(const float* const* src, const float* coef, int32_t nterms, float* out, int64_t n, v3d_stream_t stream);
 /* dst_bf16[r][dst_off + c] = src_bf16[r][src_off + c], c < C  (strided 2-D bf16 copy; C % 8 == 0) */
 int v3d_copy2d_bf16(const void* src, int64_t lds, void* dst, int64_t ldd, int64_t rows, int64_t C, v3d_stream_t stream);
 

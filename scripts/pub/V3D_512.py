@@ -102,12 +102,13 @@ def sample_one(input_path: str = "assets/test_image.png", checkpoint_path: Optio
                cond_frames: torch.Tensor = None, cond_frames_without_noise: torch.Tensor = None, image: torch.Tensor = None,
                synthetic: bool = False, clip_checkpoint_path: Optional[str] = None, clip_config=None,
                height: int = 512, width: int = 512, model_channels: int = 320, vae_ch: int = 128,
-               ae_checkpoint_path: Optional[str] = None):
+               ae_checkpoint_path: Optional[str] = None, sampler: str = "euler"):
     """Returns (frames uint8 [T, H, W, 3] on the host, model).  Keyword arguments up to `ignore_alpha` are the reference's."""
     num_frames = 18 if num_frames is None else num_frames       # the reference reads it from the guider config (18)
     num_steps = 25 if num_steps is None else num_steps
     decoding_t = min(decoding_t, num_frames)
-    cfg = config if config is not None else configs.v3d_512_config(num_frames=num_frames, num_steps=num_steps, model_channels=model_channels, vae_ch=vae_ch)
+    cfg = config if config is not None else configs.v3d_512_config(num_frames=num_frames, num_steps=num_steps, model_channels=model_channels, vae_ch=vae_ch,
+                                                                   sampler=sampler)
     if cached_model is None:
         model, _ = load_model(cfg, device, num_frames, num_steps, ckpt_path=checkpoint_path, min_cfg=min_guidance_scale,
                               max_cfg=max_guidance_scale, sigma_max=sigma_max)
@@ -230,6 +231,8 @@ def main():
     ap.add_argument("--border_ratio", type=float, default=0.3, help="reference argument of its rembg / kiui recentering step, which this build does "
                                                                     "not run: the input must already be a prepared (matted, centred) RGB view")
     ap.add_argument("--ignore_alpha", action="store_true")
+    ap.add_argument("--sampler", default="euler", choices=list(configs.SAMPLERS),
+                    help="sampler of the built-in config (default: the reference's EulerEDMSampler); ignored with --config")
     a = ap.parse_args()
     if not os.path.isfile(a.input_path) and not a.synthetic:
         raise SystemExit(f"input image {a.input_path} not found (pass --synthetic to run on synthetic conditioning)")
@@ -248,7 +251,7 @@ def main():
                            a.decoding_t, a.device, a.output_folder, save=a.save, min_guidance_scale=a.min_guidance_scale,
                            max_guidance_scale=a.max_guidance_scale, sigma_max=a.sigma_max, config=a.config, synthetic=a.synthetic, image=image,
                            clip_checkpoint_path=a.clip_checkpoint_path, ae_checkpoint_path=a.ae_checkpoint_path, border_ratio=a.border_ratio,
-                           ignore_alpha=a.ignore_alpha)
+                           ignore_alpha=a.ignore_alpha, sampler=a.sampler)
     print("frames", frames.shape, frames.dtype, "mean", float(frames.mean()))
     # parity status of what just ran: sampler / U-Net / decoder / VAE encoder are pinned to fixtures generated from the
     # reference's own modules; the OpenCLIP ViT tower is pinned to transformers' implementation of the same architecture (tests/golden/clip_tower.pt);

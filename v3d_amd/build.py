@@ -23,7 +23,9 @@ FLAGS = ["-O3", "-std=c++17", f"--offload-arch={ARCH}", "-fPIC", "-ffast-math", 
 # different slots into v_pk_*_f32 (which also cost more than they save beside MFMAs)
 # attn.hip: the compiler SLP-packs the softmax's adjacent fp32 multiplies / adds into v_pk_*_f32, which beside MFMAs cost more than the scalar
 # pairs (same-process A/B, profiles/r05_attn_ab.txt: 917 -> 914 us alone, 895 -> 874 us together with the deferred maximum)
-FILE_FLAGS = {"ff.hip": ["-fno-slp-vectorize"], "attn.hip": ["-fno-slp-vectorize"]}
+# noise.hip: the Gaussian noise of the ancestral samplers is specified with the precise logf / sincospif (tests hold it to a numpy restatement
+# at 1e-5); -ffast-math would let the compiler swap in the approximate hardware forms
+FILE_FLAGS = {"ff.hip": ["-fno-slp-vectorize"], "attn.hip": ["-fno-slp-vectorize"], "noise.hip": ["-fno-fast-math"]}
 
 
 def _hipcc() -> str:

@@ -13,9 +13,17 @@ S = "v3d_amd.sgm."
 TRAINING_ONLY_KEYS = ("scheduler_config", "loss_fn_config", "optimizer_config")
 
 
+# sampler choices of v3d_512_config / scripts/pub/V3D_512.py --sampler -> class in sgm/modules/diffusionmodules/sampling.py (default: the yaml's)
+SAMPLERS = {"euler": "EulerEDMSampler", "heun": "HeunEDMSampler", "euler_ancestral": "EulerAncestralSampler",
+            "dpmpp2s_ancestral": "DPMPP2SAncestralSampler", "dpmpp2m": "DPMPP2MSampler", "lms": "LinearMultistepSampler"}
+
+
 def v3d_512_config(num_frames: int = 18, num_steps: int = 30, min_scale: float = 3.5, max_scale: float = 3.5,
-                   sigma_max: float = 700.0, model_channels: int = 320, vae_ch: int = 128, ckpt_path=None) -> dict:
-    """{'model': {...}} equivalent of V3D_512.yaml (defaults: yaml:134-146; script overrides: V3D_512.py:84-105)."""
+                   sigma_max: float = 700.0, model_channels: int = 320, vae_ch: int = 128, ckpt_path=None, sampler: str = "euler") -> dict:
+    """{'model': {...}} equivalent of V3D_512.yaml (defaults: yaml:134-146; script overrides: V3D_512.py:84-105).  `sampler` picks
+    another sampler class of the same API (SAMPLERS); the schedule, guider and step count stay as configured."""
+    if sampler not in SAMPLERS:
+        raise ValueError(f"unknown sampler {sampler!r}; choose one of {', '.join(SAMPLERS)}")
     emb = S + "modules.encoders.modules."
     conditioner = {"target": S + "modules.GeneralConditioner", "params": {"emb_models": [
         {"is_trainable": False, "ucg_rate": 0.2, "input_key": "cond_frames_without_noise", "target": emb + "IdentityEncoder"},
@@ -38,7 +46,7 @@ def v3d_512_config(num_frames: int = 18, num_steps: int = 30, min_scale: float =
         "network_config": {"target": d + "video_model.VideoUNet", "params": synth.unet_config(model_channels)},
         "conditioner_config": conditioner,
         "first_stage_config": first_stage,
-        "sampler_config": {"target": d + "sampling.EulerEDMSampler", "params": {
+        "sampler_config": {"target": d + "sampling." + SAMPLERS[sampler], "params": {
             "num_steps": num_steps,
             "discretization_config": {"target": d + "discretizer.EDMDiscretization", "params": {"sigma_max": sigma_max}},
             "guider_config": {"target": d + "guiders.LinearPredictionGuider",

@@ -377,8 +377,10 @@ def sharded_unet_eval(net, shard: FrameShard, x, scale, concat, timesteps, conte
 
 def local_sampler(sampler, shard: FrameShard):
     """Shallow copy of a sampler whose guider applies THIS rank's slice of the per-frame guidance scale (guiders.py:61-86 index the
-    scale by global frame id)."""
+    scale by global frame id) and whose device noise (ancestral samplers, v3d_randn_add) is drawn for this rank's frames of the unsharded
+    sample: noise_frames = (t0, T_local, T_global)."""
     s = copy.copy(sampler)
+    s.noise_frames = (shard.t0, shard.T_local, shard.T_global)
     g = copy.copy(sampler.guider)
     sc = getattr(g, "scale", None)
     if isinstance(sc, torch.Tensor) and sc.numel() == shard.T_global and hasattr(g, "num_frames"):
@@ -413,6 +415,16 @@ def sharded_sample(shard: FrameShard, sampler, denoiser, network, decode, noise,
         image_only_indicator = torch.zeros(2 * B, T, device=dev)
     ioi_loc = image_only_indicator[:, shard.t0:shard.t0 + Tl].contiguous()
     smp = local_sampler(sampler, shard)
+    if hasattr(smp, "noise_seed") and smp.noise_seed is None:
+        # a stochastic sampler draws its seed per call: every rank draws (the generators advance as in an unsharded run), rank 0's draw is
+        # agreed by one tiny sum (the others contribute 0) so that all ranks add the noise of ONE unsharded sample.  A HybridShard sums
+        # over the whole job (its shard has no sub-group), so only the first rank of cfg group 0 contributes; its partners get that seed too.
+        from .sgm.modules.diffusionmodules.sampling import draw_noise_seed
+        seed = draw_noise_seed()
+        lead = shard.rank == 0 and getattr(shard, "cfg_index", 0) == 0
+        agreed = torch.tensor([seed if lead else 0], dtype=torch.int64, device=dev)
+        shard._allreduce_sum(agreed)
+        smp.noise_seed = int(agreed.item())
     if isinstance(shard, HybridShard):
         # cfg-parallel x frame-shard: this rank's frame group evaluates ONE half of the guided batch [uc ; c] (B samples instead of 2 B),
         # the partner rank of the other group the other half; the halves are swapped once per evaluation and the guider / sampler update

@@ -16,7 +16,7 @@ from .ops import GemmCall, OpsBase
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("V3D_HIP_LIB") or os.path.join(_HERE, "lib", "libv3d_hip.so")     # (override: A/B runs of two builds on one box)
 
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 c_i64, c_i32, c_f32, c_f64, c_vp = C.c_int64, C.c_int32, C.c_float, C.c_double, C.c_void_p
 
@@ -90,6 +90,8 @@ SIGNATURES = {
     "v3d_nchw_to_nhwc_bf16": (c_i32, [c_vp, c_f32, c_vp, c_i64, c_i64, c_i64, c_i64, c_vp]),
     "v3d_tmix_small": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_i32, c_i64, c_i32, c_i32, c_i32, c_i64, c_vp]),
     "v3d_copy2d_bf16": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i64, c_i64, c_vp]),
+    "v3d_randn_add": (c_i32, [c_vp, c_f32, C.c_uint64, C.c_uint32, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_vp]),
+    "v3d_lincomb_f32": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_i64, c_vp]),
 }
 
 
@@ -620,6 +622,48 @@ class HipOps(OpsBase):
         if out is None:
             out = torch.empty_like(x)
         self._check(self.lib.v3d_axpb_f32(x.data_ptr(), float(a), float(b), out.data_ptr(), x.numel(), self._stream()), "v3d_axpb_f32")
+        return out
+
+    def randn_add(self, x, scale, seed, call, *, t0=0, T_local=None, T_global=None, out=None):
+        """out = (x or 0) + scale * N(seed, call, global element index), N = counter-based Philox Gaussian noise (csrc/noise.hip).
+        Rows are frames [(b T_local), ...]; (t0, T_local, T_global) place them in the unsharded [(b T_global), ...] tensor (default: the
+        tensor is the whole one).  x = None: pure noise into `out`.  out may be x."""
+        f32 = torch.float32
+        ref = x if x is not None else out
+        if ref is None:
+            raise RuntimeError("randn_add: give x or out")
+        self._req_c(ref, f32, "randn_add.x")
+        if out is None:
+            out = torch.empty_like(x)
+        self._req_c(out, f32, "randn_add.out")
+        if out.shape != ref.shape:
+            raise RuntimeError(f"randn_add: out {tuple(out.shape)} != x {tuple(ref.shape)}")
+        rows = ref.shape[0]
+        T_local = rows if T_local is None else int(T_local)
+        T_global = T_local if T_global is None else int(T_global)
+        if rows % T_local:
+            raise RuntimeError(f"randn_add: {rows} rows are not a whole number of {T_local}-frame samples")
+        self._check(self.lib.v3d_randn_add(_ptr(x), float(scale), int(seed) & 0xFFFFFFFFFFFFFFFF, int(call) & 0xFFFFFFFF, out.data_ptr(),
+                                           rows // T_local, T_local, T_global, int(t0), ref.numel() // rows, self._stream()), "v3d_randn_add")
+        return out
+
+    def lincomb_f32(self, srcs, coefs, out=None):
+        """out = sum_k coefs[k] * srcs[k] (fp32, same shapes, 1..6 terms; out may be one of the sources)."""
+        if not 1 <= len(srcs) <= 6 or len(srcs) != len(coefs):
+            raise RuntimeError(f"lincomb_f32: {len(srcs)} sources / {len(coefs)} coefficients (1..6 terms)")
+        for k, t in enumerate(srcs):
+            self._req_c(t, torch.float32, f"lincomb.src{k}")
+            if t.shape != srcs[0].shape:
+                raise RuntimeError(f"lincomb_f32: source {k} has shape {tuple(t.shape)} != {tuple(srcs[0].shape)}")
+        if out is None:
+            out = torch.empty_like(srcs[0])
+        self._req_c(out, torch.float32, "lincomb.out")
+        if out.shape != srcs[0].shape:
+            raise RuntimeError(f"lincomb_f32: out {tuple(out.shape)} != {tuple(srcs[0].shape)}")
+        ptrs = (c_vp * len(srcs))(*[t.data_ptr() for t in srcs])
+        cf = (c_f32 * len(srcs))(*[float(c) for c in coefs])
+        self._check(self.lib.v3d_lincomb_f32(C.cast(ptrs, c_vp), C.cast(cf, c_vp), len(srcs), out.data_ptr(), out.numel(), self._stream()),
+                    "v3d_lincomb_f32")
         return out
 
     def blend_coefs(self, alpha, kind, ioi, n_img):

@@ -139,7 +139,7 @@ def case_gemm(hip, emu, dev, *, M, N, K, mode=GEMM_LINEAR, geglu=False, bias=Tru
         return compare(out_h, out_e)
     sk0 = _sk_counter(hip, "v3d_debug_sk_launches") if expect_streamk is not None else 0
     hip.gemm(GemmCall(out=out_h, **base))
-    if expect_family is not None and getattr(hip, "name", "") == "hip" and not any(os.environ.get(k) for k in ("V3D_GEMM_IMPL", "V3D_GEMM_CFG", "V3D_GEMM_V6")):
+    if expect_family is not None and getattr(hip, "name", "") == "hip" and not any(os.environ.get(k) for k in ("V3D_GEMM_IMPL", "V3D_GEMM_V6")):
         # the dispatcher's choice under the default policy (gemm.hip dispatch): 6 = two persistent 4-wave blocks per CU on 192 x 160 tiles
         fam = hip.last_gemm_launch()["family"]
         assert fam == expect_family, f"expected kernel family {expect_family}, the library launched {hip.last_gemm_launch()}"

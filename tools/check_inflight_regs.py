@@ -2,15 +2,15 @@
 has in flight.  The residual look-ahead loads are asm (the compiler does not know their destinations are pending) and their waits are counted
 asm s_waitcnt vmcnt(N) that NAME the registers they cover; everything is correct as long as the register allocator leaves those registers alone
 between the load and its wait.  Passing the pieces by value through the unrolled fragments can make it insert a v_mov of such a register
-(seen with E4_DEPTH_LINEAR=3 once the compiler's own vmcnt(0) drains were gone: wrong results, profiles/r06_e4_asm_reads_ab.txt) - this script
+(seen with a three-fragment look-ahead once the compiler's own vmcnt(0) drains were gone: wrong results, profiles/r06_e4_asm_reads_ab.txt) - this script
 finds that in the disassembly.  Scan per kernel in program order: VMEM operations are numbered as they appear and an s_waitcnt vmcnt(N) retires all
 but the N youngest; forward branches carry the set of pending registers to their labels (the code behind an unconditional branch starts from what
 its own label receives), backward branches are ignored (the main loops hold no asm loads).
-Known false positive (product build): the two multi-tap <.., 1, .., true> GroupNorm-statistics kernels of gemm.hip are reported through a path that takes the
+Known false positive (product build): multi-tap GroupNorm-statistics kernels of gemm.hip (gemm_kernel_v3<256, 256, .., true>) are reported through a path that takes the
 `no residual operand` branch around a counted wait AFTER having issued residual loads (the test is launch-invariant; the scanner only recognises
-the simple forms of that correlation).  What a real finding looks like: v_mov_b64 copies whose SOURCE is pending (EXTRA_FLAGS="-DE4_DEPTH_LINEAR=3").
+the simple forms of that correlation).  What a real finding looks like: v_mov_b64 copies whose SOURCE is pending.
 usage: python tools/check_inflight_regs.py v3d_amd/csrc/gemm.hip [kernel-name-substring ...]      (--strict as first argument: exit code 1 on a finding)
-       EXTRA_FLAGS="-DE4_DEPTH_LINEAR=3" python tools/check_inflight_regs.py v3d_amd/csrc/gemm.hip          audit an A/B build"""
+       EXTRA_FLAGS="-DCONV_3X3_READS=2" python tools/check_inflight_regs.py v3d_amd/csrc/conv.hip          audit an A/B build"""
 import os
 import re
 import subprocess

@@ -1,4 +1,4 @@
-"""Per-tile fixed cost of a v3d_gemm configuration: time vs K at fixed M, N (env V3D_GEMM_IMPL / _CFG / _ABLATE)."""
+"""Per-tile fixed cost of a v3d_gemm configuration: time vs K at fixed M, N (env V3D_GEMM_IMPL)."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -18,4 +18,4 @@ for K in (32, 64, 160, 320, 640, 1280):
     call = GemmCall(A=A, W=W, out=o, M=M, N=N, K=K, bias=torch.randn(N, device="cuda"), mode=GEMM_LINEAR, geglu=GEGLU, **kw)
     ms = timeit(lambda: hip.gemm(call), iters=10)
     out.append(f"K{K}={ms * 1e3:.0f}us")
-print(f"[N={N} geglu={int(GEGLU)} res={int(RES)} impl={os.environ.get('V3D_GEMM_IMPL', '0')} cfg={os.environ.get('V3D_GEMM_CFG', '-')} abl={os.environ.get('V3D_GEMM_ABLATE', '0')}] " + " ".join(out))
+print(f"[N={N} geglu={int(GEGLU)} res={int(RES)} impl={os.environ.get('V3D_GEMM_IMPL', '0')}] " + " ".join(out))

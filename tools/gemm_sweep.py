@@ -1,5 +1,5 @@
-"""A/B sweep of v3d_gemm configurations (env V3D_GEMM_IMPL / V3D_GEMM_CFG, read once per process) on V3D shapes.
-Usage: for c in 0 1 2 3 4; do V3D_GEMM_CFG=$c python tools/gemm_sweep.py; done"""
+"""TF/s of v3d_gemm on V3D shapes under the default dispatch or a forced family (env V3D_GEMM_IMPL / V3D_GEMM_V6 / ..., read once per process).
+Usage: for i in 1 2 3; do V3D_GEMM_IMPL=$i python tools/gemm_sweep.py; done      --check: parity of every GEMM case of tests/op_cases.py first"""
 import os
 import sys
 
@@ -14,7 +14,7 @@ from tools.gpu_check import timeit  # noqa: E402
 
 BF = torch.bfloat16
 hip = HipOps()
-tag = f"impl={os.environ.get('V3D_GEMM_IMPL', '2')} cfg={os.environ.get('V3D_GEMM_CFG', '-')} abl={os.environ.get('V3D_GEMM_ABLATE', '0')}"
+tag = f"impl={os.environ.get('V3D_GEMM_IMPL', '0')}"
 if "--check" in sys.argv:
     import op_cases
     from oracle.ops_emul import EmulOps

@@ -1,5 +1,5 @@
 """GroupNorm statistics in the producing GEMM's epilogue vs the stand-alone pass, isolated launches at the V3D_512 level-0 / level-1 shapes.
-   python tools/gn_epi_bench.py        (V3D_GEMM_ABLATE=1024: epilogue without its atomics)"""
+   python tools/gn_epi_bench.py"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)

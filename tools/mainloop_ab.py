@@ -2,7 +2,8 @@
 (cdna_hip_programming.md rule 24: N variants x M rounds in one process; median and min per variant).  Every build's output is also compared
 with the first build's (max abs difference: pure scheduling variants must agree bit for bit).
 
-  python tools/mainloop_ab.py base=v3d_amd/lib/libv3d_hip.so m1=v3d_amd/lib_exp/libv3d_m1.so ... [--only=substr,...] [--rounds=5]
+  python tools/mainloop_ab.py base=<parent build>/libv3d_hip.so new=v3d_amd/lib/libv3d_hip.so ... [--only=substr,...] [--rounds=5]
+  (tools/build_variant.sh builds compile-time variants into v3d_amd/lib_exp/)
 -> gpurun_out/mainloop_ab.json + a table on stdout (us per launch, TF/s of the first build)."""
 from __future__ import annotations
 

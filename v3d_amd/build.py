@@ -35,14 +35,8 @@ def _hipcc() -> str:
     raise RuntimeError("hipcc not found (need ROCm >= 7.0 to build the gfx950 kernels)")
 
 
-LAB = os.path.join(os.path.dirname(HERE), "tools", "lab")     # lab-only kernels (round-4 gemm4.hip): linked into the experiments library only
-
-
-def sources(experiments: bool = False):
-    src = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hip"))
-    if experiments and os.path.isdir(LAB):
-        src += sorted(os.path.join(LAB, f) for f in os.listdir(LAB) if f.endswith(".hip"))
-    return src
+def sources():
+    return sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hip"))
 
 
 def _stale(out: str, deps) -> bool:
@@ -52,23 +46,13 @@ def _stale(out: str, deps) -> bool:
     return any(os.path.getmtime(d) > t for d in deps)
 
 
-def build(force: bool = False, verbose: bool = True, experiments: bool = False) -> str:
-    """experiments=True: a second library (lib_exp/libv3d_hip_exp.so, -DV3D_EXPERIMENTS) whose GEMM / convolution kernels honour the
-    V3D_GEMM_ABLATE timing switches (skip MFMAs / DMA / fragment reads / barriers: results are garbage by design).  Select it with
-    V3D_HIP_LIB=<path>; the product library never contains those switches."""
-    if experiments:
-        return _build(force, verbose, os.path.join(HERE, "lib_exp"), "libv3d_hip_exp.so", ["-DV3D_EXPERIMENTS"])
-    return _build(force, verbose, LIBDIR, "libv3d_hip.so", [])
-
-
-def _build(force, verbose, LIBDIR, libname, extra) -> str:
-    LIB = os.path.join(LIBDIR, libname)
+def build(force: bool = False, verbose: bool = True) -> str:
     os.makedirs(LIBDIR, exist_ok=True)
     hipcc = _hipcc()
     hdrs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
     hdrs.append(os.path.join(os.path.dirname(HERE), "include", "v3d_hip.h"))
     objs, jobs = [], []
-    for src in sources(experiments=bool(extra)):
+    for src in sources():
         obj = os.path.join(LIBDIR, os.path.basename(src)[:-4] + ".o")
         objs.append(obj)
         if force or _stale(obj, [src] + hdrs):
@@ -76,7 +60,7 @@ def _build(force, verbose, LIBDIR, libname, extra) -> str:
 
     def cc(job):
         src, obj = job
-        cmd = [hipcc, *FLAGS, *extra, *FILE_FLAGS.get(os.path.basename(src), []), "-I", CSRC, "-c", src, "-o", obj]
+        cmd = [hipcc, *FLAGS, *FILE_FLAGS.get(os.path.basename(src), []), "-I", CSRC, "-c", src, "-o", obj]
         if verbose:
             print("[v3d_amd.build]", " ".join(cmd), flush=True)
         r = subprocess.run(cmd, capture_output=True, text=True)
@@ -95,13 +79,12 @@ def _build(force, verbose, LIBDIR, libname, extra) -> str:
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError(f"link failed:\n{r.stdout}\n{r.stderr}")
-    if not extra:
-        # libv3d_comm.so is OPTIONAL: the Python product path never loads it (dist.py runs the same schedule on torch.distributed), and a box
-        # without rccl.h / librccl under the ROCm tree must still get the kernel library
-        try:
-            build_comm(force=force, verbose=verbose)
-        except Exception as e:      # noqa: BLE001
-            print(f"[v3d_amd.build] WARNING: libv3d_comm.so not built ({str(e).splitlines()[0]}); the kernel library is unaffected", file=sys.stderr)
+    # libv3d_comm.so is OPTIONAL: the Python product path never loads it (dist.py runs the same schedule on torch.distributed), and a box
+    # without rccl.h / librccl under the ROCm tree must still get the kernel library
+    try:
+        build_comm(force=force, verbose=verbose)
+    except Exception as e:      # noqa: BLE001
+        print(f"[v3d_amd.build] WARNING: libv3d_comm.so not built ({str(e).splitlines()[0]}); the kernel library is unaffected", file=sys.stderr)
     return LIB
 
 
@@ -127,4 +110,4 @@ def build_comm(force: bool = False, verbose: bool = True) -> str:
 
 
 if __name__ == "__main__":
-    print(build(force="--force" in sys.argv, experiments="--experiments" in sys.argv))
+    print(build(force="--force" in sys.argv))

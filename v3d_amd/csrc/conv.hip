@@ -598,7 +598,7 @@ __global__ __launch_bounds__(512, 2) void conv_halo_kernel(GP p, int ntiles) {
             // kernels keep the compiler-visible reads and their vmcnt(0) drains: once the in-place ds_write of the normalisation chain had freed their registers the
             // lean form fits all but the <W = 32, GroupNorm operand, no statistics> variant (tools/check_loop_scratch.py), but with 90-360 steps per tile the
             // drains are not what their epilogue costs - -DCONV_3X3_READS=2 measured +-1 % on five launch classes and +6 % on one (profiles/r06_conv_w8_ab.txt)
-            e4_retire_tile<MF, NF, GN, E4_DEPTH, (HM == HM_TEMP ? CONV_TEMP_READS : (W_ == 32 && XF && !GN ? 0 : CONV_3X3_READS))>(p, acc, nw0, lane_e, estage, rowfn, flushfn);
+            e4_retire_tile<MF, NF, GN, (HM == HM_TEMP ? CONV_TEMP_READS : (W_ == 32 && XF && !GN ? 0 : CONV_3X3_READS))>(p, acc, nw0, lane_e, estage, rowfn, flushfn);
         }
 #pragma unroll
         for (int i = 0; i < MF; ++i)

@@ -24,22 +24,13 @@
 
 #include "gemm_common.h"
 
-// Tile walk / tap order knobs (same-box A/B: tools/gemm_ab.sh, profiles/r02b_gemm_ab.txt):
-//   V3D_GEMM_GROUPM   -1 heuristic (default), 0 = row-major walk, n = groups of n tile rows.  Measured (TF/s, row-major -> 4 -> 8): GEGLU projection
-//                     N = 10240: 824 -> 877 -> 861, N = 5120: 714 -> 703 -> 737; temporal qkv N = 3840: 674 -> 738 -> 726; the feed-forward
-//                     out-projections +3 %; convolutions (N <= 5 tile columns) +-2 %.  Heuristic: 8 for >= 96 tile rows, else 4.
-//   V3D_GEMM_TAPINNER 1 = (k outer, tap inner) stage order.  It removes the 7-19x L2-miss re-reads of the K >= 640 convolutions but recomputes
-//                     the per-lane row offsets every 32-k step: 25-30 % SLOWER on every convolution (1044 -> 769 TF/s at 1920 -> 640) - the
-//                     loaders have no VALU to spare, the re-reads come from the Infinity Cache and are not what bounds these launches.  Off.
-#ifndef V3D_GEMM_V6_DEFAULT
-#define V3D_GEMM_V6_DEFAULT 1
-#endif
-#ifndef V3D_GEMM_V6_MIN_TILES
-#define V3D_GEMM_V6_MIN_TILES 512
-#endif
-#ifndef V3D_GEMM_TAPINNER_DEFAULT
-#define V3D_GEMM_TAPINNER_DEFAULT 0
-#endif
+// Tile walk and stage order (same-box A/B, profiles/r02b_gemm_ab.txt):
+//   tile walk (V3dGemmParams::group_m, tile_coords): groups of 8 tile rows for >= 96 tile rows, else 4; v6 walks row-major.  Measured (TF/s,
+//     row-major -> 4 -> 8): GEGLU projection N = 10240: 824 -> 877 -> 861, N = 5120: 714 -> 703 -> 737; temporal qkv N = 3840: 674 -> 738 -> 726;
+//     the feed-forward out-projections +3 %; convolutions (N <= 5 tile columns) +-2 %.
+//   stage order: (tap outer, k inner).  (k outer, tap inner) removes the 7-19x L2-miss re-reads of the K >= 640 convolutions but recomputes the
+//     per-lane row offsets every 32-k step: 25-30 % SLOWER on every convolution (1044 -> 769 TF/s at 1920 -> 640) - the loaders have no VALU to
+//     spare, the re-reads come from the Infinity Cache and are not what bounds these launches.
 
 namespace {
 
@@ -128,9 +119,8 @@ __global__ __launch_bounds__(64 * WGM * WGN, (64 * WGM * WGN) == 256 ? 2 : 1) vo
     const int s0 = p.split_n > 1 ? (int)((long long)total_steps * blockIdx.y / p.split_n) : 0;
     const int s1 = p.split_n > 1 ? (int)((long long)total_steps * (blockIdx.y + 1) / p.split_n) : total_steps;
     const int nsteps = s1 - s0;
-    const bool tap_inner = ntaps<MODE>() > 1 && p.tap_inner;
-    int ld_tap = tap_inner ? s0 % ntaps<MODE>() : s0 / ksteps;
-    int ld_k0 = tap_inner ? (s0 / ntaps<MODE>()) * BK2 : (s0 - ld_tap * ksteps) * BK2;
+    int ld_tap = s0 / ksteps;
+    int ld_k0 = (s0 - ld_tap * ksteps) * BK2;
     set_tap(ld_tap);
     // steps issued past the end of the contraction (ring tail) re-read valid rows of the last tap: harmless dummies that
     // keep the per-wave DMA count per stage constant for the counted vmcnt waits
@@ -142,15 +132,6 @@ __global__ __launch_bounds__(64 * WGM * WGN, (64 * WGM * WGN) == 256 ? 2 : 1) vo
 #pragma unroll
         for (int i = 0; i < BPW; ++i)
             __builtin_amdgcn_global_load_lds((const void*)(brow[i] + ld_k0), (__attribute__((address_space(3))) void*)(sbase + BM * ROWB + (wave + NW * i) * 1024), 16, 0, 0);
-        if (tap_inner) {   // (k outer, tap inner): the nine taps of a k-slice follow each other while their rows are still in L2
-            if (++ld_tap >= ntaps<MODE>()) {
-                ld_tap = 0;
-                ld_k0 += BK2;
-                if (ld_k0 >= p.K) ld_k0 = 0;   // (ring-tail dummies)
-            }
-            set_tap(ld_tap);
-            return;
-        }
         ld_k0 += BK2;
         if (ld_k0 >= p.K) {
             ld_k0 = 0;
@@ -176,7 +157,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, (64 * WGM * WGN) == 256 ? 2 : 1) vo
 
     // main-loop waves outrank co-resident blocks that are in their (VALU-dense) epilogue: without it the two do not overlap -
     // time(K) = time(epilogue only) + time(main loop only) on the GEGLU projections (tools/gemm_floor.py)
-    if (!V3D_ABL(p, 64)) __builtin_amdgcn_s_setprio(2);
+    __builtin_amdgcn_s_setprio(2);
     for (int t = 0; t < nsteps; ++t) {
         // this wave's pieces of stage t have landed when at most PIECES*(NS-2) newer DMA ops are outstanding
         asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PIECES * (NS - 2)) : "memory");
@@ -328,10 +309,7 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel_v1(GP p) {
 //   * counted s_waitcnt vmcnt(8): two younger stages (4 DMA ops each per wave) may stay in flight; epilogue stores in
 //     flight only make the count conservative (loads return in order among themselves).
 
-// slot-level timeline of the v3 loop (V3D_GEMM_ABLATE bit 8, LINEAR only): [group][step 32..63][stamp] s_memtime ticks
-__device__ unsigned long long g_v3_dbg[2 * 32 * 8];
-
-template <int BM, int BN, int WGM, int WGN, int MODE, bool GEGLU, int EMF, bool DBG = false, int NS = 4, int SPAD = 16, bool GN = false>
+template <int BM, int BN, int WGM, int WGN, int MODE, bool GEGLU, int EMF, int NS = 4, int SPAD = 16, bool GN = false>
 __global__ __launch_bounds__(512, NS == 3 ? 4 : 2) void gemm_kernel_v3(GP p, int ntiles) {   // (HIP: 2nd arg = min waves per SIMD)
     // NS = 4: one block per CU (128 KiB ring).  NS = 3 with a 256 x 128 tile: 72 KiB ring + 8 KiB staging = 80 KiB -> TWO blocks per
     // CU (128 VGPRs per wave), so one block's VALU-bound epilogue (GEGLU) overlaps the other block's main loop.
@@ -347,17 +325,12 @@ __global__ __launch_bounds__(512, NS == 3 ? 4 : 2) void gemm_kernel_v3(GP p, int
     constexpr int STAGE_BYTES = (BM + BN) * ROWB;
     constexpr int NFO = GEGLU ? NF / 2 : NF;
     constexpr int EPI_REGION = EMF * 16 * (NFO * 32 + SPAD);
-    __shared__ __attribute__((aligned(1024))) unsigned char lds[NS * STAGE_BYTES + NW * EPI_REGION + (DBG ? 4096 : 0)];
+    __shared__ __attribute__((aligned(1024))) unsigned char lds[NS * STAGE_BYTES + NW * EPI_REGION];
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int grp = wave >> 2;
-    unsigned long long* dbg = reinterpret_cast<unsigned long long*>(lds + NS * STAGE_BYTES + NW * EPI_REGION);
-    const bool dbg_on = DBG && blockIdx.x == 0 && (wave & 3) == 0;
-    auto stamp = [&](int s_, int k) __attribute__((always_inline)) {
-        if (DBG && dbg_on && s_ >= 32 && s_ < 64 && lane == 0) dbg[(grp * 32 + (s_ - 32)) * 8 + k] = __builtin_amdgcn_s_memtime();
-    };
     const int wm = wave / WGN, wn = wave % WGN;
     const bf16_t* __restrict__ A = p.A;
     const bf16_t* __restrict__ W = p.W;
@@ -370,7 +343,7 @@ __global__ __launch_bounds__(512, NS == 3 ? 4 : 2) void gemm_kernel_v3(GP p, int
         int tm, tn;
         tile_coords(p, id, tm, tn);
         n0 = (long long)tn * BN;
-        m0 = p.m_off + (long long)tm * BM;
+        m0 = (long long)tm * BM;
     };
 
     // ---- loader state (runs up to 3 stages ahead of the consumer, across tile boundaries).  Raw buffer loads straight to
@@ -410,31 +383,10 @@ __global__ __launch_bounds__(512, NS == 3 ? 4 : 2) void gemm_kernel_v3(GP p, int
     };
     set_tile(0);
     auto issue_piece = [&](int stage, int i, int so) __attribute__((always_inline)) {
-        if V3D_ABL(p, 4) return;
         const int q = wave + NW * i;
-        // experiment (bit 2048): activation pieces issued out of range - same DMA op count, zeros instead of an L2 fetch: what the L2->LDS bytes
-        // of the activation operand cost (a lower bound of what an LDS-resident halo tile would save a 3x3 convolution)
-        const unsigned vo = (V3D_ABL(p, 2048) && q < APIECES) ? kInvalid : voff[i];
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(q < APIECES ? rsA : rsW, (__attribute__((address_space(3))) void*)(lds + stage * STAGE_BYTES + q * 1024), 16, (int)vo, so, 0, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(q < APIECES ? rsA : rsW, (__attribute__((address_space(3))) void*)(lds + stage * STAGE_BYTES + q * 1024), 16, (int)voff[i], so, 0, 0);
     };
     auto issue_advance = [&]() __attribute__((always_inline)) {
-        if (ntaps<MODE>() > 1 && p.tap_inner) {   // (k outer, tap inner), see the v2 loader
-            if (++ld_tap < ntaps<MODE>()) {
-                set_tap(ld_tap);
-                return;
-            }
-            ld_tap = 0;
-            ld_k0 += 32;
-            if (ld_k0 >= (int)p.K) {
-                ld_k0 = 0;
-                if (++ld_it < my_tiles) {
-                    set_tile(ld_it);
-                    return;
-                }
-            }
-            set_tap(0);
-            return;
-        }
         ld_k0 += 32;
         if (ld_k0 >= (int)p.K) {
             ld_k0 = 0;
@@ -481,7 +433,6 @@ __global__ __launch_bounds__(512, NS == 3 ? 4 : 2) void gemm_kernel_v3(GP p, int
     int rd = 0;       // ring slot of step s; the refill target (step s + NS - 1) is the slot before it
     for (int it = 0; it < my_tiles; ++it) {
         for (int kt = 0; kt < nsteps; ++kt, ++s) {
-            stamp(s, 0);
             {
                 const unsigned char* sb = lds + rd * STAGE_BYTES;
 #pragma unroll
@@ -493,37 +444,30 @@ __global__ __launch_bounds__(512, NS == 3 ? 4 : 2) void gemm_kernel_v3(GP p, int
             // fragment reads are in flight
             issue(rd == 0 ? NS - 1 : rd - 1);
             rd = (rd + 1 == NS) ? 0 : rd + 1;
-            stamp(s, 1);
             // group 1 must have its fragments in registers before it passes the barrier (the slot is refilled after it);
             // group 0 goes straight into its MFMAs and lets the compiler's counted lgkmcnt waits release them fragment by fragment
-            if (grp == 1 || V3D_ABL(p, 512)) {
+            if (grp == 1) {
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 __builtin_amdgcn_sched_barrier(0);
             }
-            stamp(s, 2);
             if (grp == 1) {
                 asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PPW * (NS - 2)) : "memory");   // own pieces of stage s+1 landed
                 __builtin_amdgcn_s_barrier();
                 __builtin_amdgcn_sched_barrier(0);
             }
-            stamp(s, 3);
-            if (!V3D_ABL(p, 256)) __builtin_amdgcn_s_setprio(1);
-            if (!V3D_ABL(p, 2)) {
+            __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-                for (int i = 0; i < MF; ++i)
+            for (int i = 0; i < MF; ++i)
 #pragma unroll
-                    for (int j = 0; j < NF; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[j], xf[i], acc[i][j], 0, 0, 0);
-            }
-            if (!V3D_ABL(p, 256)) __builtin_amdgcn_s_setprio(0);
-            stamp(s, 4);
+                for (int j = 0; j < NF; ++j)
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[j], xf[i], acc[i][j], 0, 0, 0);
+            __builtin_amdgcn_s_setprio(0);
             __builtin_amdgcn_sched_barrier(0);
             if (grp == 0) {
                 asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PPW * (NS - 2)) : "memory");   // own pieces of stage s+1 landed
                 __builtin_amdgcn_s_barrier();
             }
             __builtin_amdgcn_sched_barrier(0);
-            stamp(s, 5);
         }
         // ---------------- tile finished for this group: retire it while the other group keeps the MFMA pipe busy
         long long e_m0, e_n0;
@@ -539,7 +483,7 @@ __global__ __launch_bounds__(512, NS == 3 ? 4 : 2) void gemm_kernel_v3(GP p, int
                 E4GnRun<WM, MF> run;
                 if constexpr (GN) run.init(mw0, p.gn_rps);
                 auto flushfn = [&](int f, long long, unsigned& slot, unsigned& sid) __attribute__((always_inline)) -> bool { return run.step(f, slot, sid); };
-                e4_retire_tile<MF, NF, GN, (MODE == V3D_GEMM_LINEAR ? E4_DEPTH_LINEAR : E4_DEPTH)>(p, acc, nw0, lane_e, estage, rowfn, flushfn);
+                e4_retire_tile<MF, NF, GN>(p, acc, nw0, lane_e, estage, rowfn, flushfn);
             }
         } else
         {
@@ -572,8 +516,6 @@ __global__ __launch_bounds__(512, NS == 3 ? 4 : 2) void gemm_kernel_v3(GP p, int
             for (int j = 0; j < NF; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (DBG && dbg_on && lane < 32)
-        for (int k = 0; k < 8; ++k) g_v3_dbg[(grp * 32 + lane) * 8 + k] = dbg[(grp * 32 + lane) * 8 + k];
 }
 
 // =====================================================================================================================
@@ -616,7 +558,7 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel_v6(GP p, int ntiles) {
         int tm, tn;
         tile_coords(p, id, tm, tn);
         n0 = (long long)tn * BN;
-        m0 = p.m_off + (long long)tm * BM;
+        m0 = (long long)tm * BM;
     };
     // ---- loader (as v3): piece q = wave + 4 i: q < APIECES activation rows, q < NPIECE weight rows, else a dummy into its own KiB
     const bufrsrc_t rsA = make_rsrc(p.A, p.a_bytes);
@@ -658,9 +600,7 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel_v6(GP p, int ntiles) {
         for (int i = 0; i < PPW; ++i) {
             const int q = wave + NW * i;
             const int dst = q < NPIECE ? stage * STAGE_BYTES + q * 1024 : DUMMY_OFF + (q - NPIECE) * 1024;
-            if V3D_ABL(p, 4) continue;
-            const unsigned vo = (V3D_ABL(p, 2048) && q < APIECES) ? kInvalid : voff[i];      // (experiments: no fetch of the activation rows)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(q < APIECES ? rsA : rsW, (__attribute__((address_space(3))) void*)(lds + dst), 16, (int)vo, so, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(q < APIECES ? rsA : rsW, (__attribute__((address_space(3))) void*)(lds + dst), 16, (int)voff[i], so, 0, 0);
         }
         ld_k0 += 32;
         if (ld_k0 >= (int)p.K) {
@@ -706,7 +646,7 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel_v6(GP p, int ntiles) {
             for (int i = 0; i < MF; ++i)
 #pragma unroll
                 for (int j = 0; j < NF; ++j)
-                    if (!V3D_ABL(p, 2)) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[j], xf[i], acc[i][j], 0, 0, 0);
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[j], xf[i], acc[i][j], 0, 0, 0);
             __builtin_amdgcn_s_setprio(0);
             __builtin_amdgcn_sched_barrier(0);
             asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PPW * (NS - 2)) : "memory");   // own pieces of the next stage landed
@@ -721,7 +661,7 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel_v6(GP p, int ntiles) {
             asm volatile("" : "+v"(lane_e));          // (keeps what the epilogue derives from the lane id out of the loop-invariant set: no spills)
             auto rowfn = [&](int f) __attribute__((always_inline)) -> long long { return mw0 + f * 16; };
             auto flushfn = [&](int, long long, unsigned&, unsigned&) __attribute__((always_inline)) -> bool { return false; };
-            e4_retire_tile<MF, NF, false, (MODE == V3D_GEMM_LINEAR ? E4_DEPTH_V6 : 1)>(p, acc, nw0, lane_e, estage, rowfn, flushfn);
+            e4_retire_tile<MF, NF, false>(p, acc, nw0, lane_e, estage, rowfn, flushfn);
         }
 #pragma unroll
         for (int i = 0; i < MF; ++i)
@@ -824,16 +764,6 @@ int impl_choice() {
     }
     return v;
 }
-// tuning knob for A/B sweeps (tools/gemm_sweep.py): forces one v2 tile / pipeline configuration (-1 = heuristic)
-int cfg_choice() {
-    static int v = -2;
-    if (v == -2) {
-        const char* e = getenv("V3D_GEMM_CFG");
-        v = e ? atoi(e) : -1;
-    }
-    return v;
-}
-
 int splitk_choice() {
     static int v = -2;
     if (v == -2) {
@@ -887,82 +817,31 @@ int launch(const GP& p0, int batch, hipStream_t st) {
         V3D_LAUNCH(1, BM, BN, (long long)grid.x * grid.y, (gemm_kernel_v1<BM, BN, MODE, GEGLU>), grid, 256, st, p);
         return v3d_check_launch("v3d_gemm");
     }
-    int cfg = cfg_choice();
-    if (cfg < 0) {
-        // measured on MI355X (profiles/r01_gemm_sweep.txt): short contractions (<= 40 stages of 32: every K <= 1280 linear,
-        // the 128-channel VAE convs) are bound by per-tile fill/drain bubbles -> more co-resident blocks (3-deep ring of
-        // BK 32, 48 KiB LDS, 3 blocks/CU) wins; long ones prefer fewer barriers per MFMA (2 stages of BK 64).
-        const long long stages32 = (long long)ntaps<MODE>() * ((p.K + 31) / 32);
-        cfg = stages32 <= 40 ? 2 : 1;
-        // 64-wide N tiles (N = 320 and friends): a 256 x 64 tile with the 4 waves stacked along M doubles the MFMAs per
-        // barrier and halves the weight re-reads (lin_L0_320x320 433 -> 487, convt_L0_320 568 -> 734 TF/s)
-        if (BN == 64) cfg = (p.K % 64 == 0) ? 9 : 8;
-        // wide GEGLU projections at K >= 640 and the 128-channel VAE convs: 256 x 128 tile on 4 waves (wave tile 128 x 64,
-        // 32 MFMAs per barrier, 25 % fewer LDS-fill bytes per flop): lin_L1_ff1_geglu 662 -> 779, lin_L2_ff1_geglu 708 -> 865
-        if (BN == 128 && ((GEGLU && p.K >= 640) || (MODE == V3D_GEMM_CONV3X3 && p.K <= 128)) && p.M >= 4096) cfg = 11;
+    if constexpr (BN == 64) {
+        // 64-wide N tiles (N = 320 and friends): a 256 x 64 tile with the 4 waves stacked along M (wave tile 64 x 64) doubles the MFMAs per
+        // barrier and halves the weight re-reads (lin_L0_320x320 433 -> 487, convt_L0_320 568 -> 734 TF/s); BK 64 x 2 stages, BK 32 x 3 when K % 64 != 0
+        p.mt = (int)((p.M + 255) / 256);
+        const dim3 g2((unsigned)(p.mt * p.nt), (unsigned)batch, 1);
+        if (p.K % 64 == 0)
+            V3D_LAUNCH(2, 256, 64, (long long)g2.x * g2.y, (gemm_kernel_v2<256, 64, 4, 1, 2, 2, MODE, GEGLU>), g2, 256, st, p);
+        else
+            V3D_LAUNCH(2, 256, 64, (long long)g2.x * g2.y, (gemm_kernel_v2<256, 64, 4, 1, 3, 1, MODE, GEGLU>), g2, 256, st, p);
+    } else if (((GEGLU && p.K >= 640) || (MODE == V3D_GEMM_CONV3X3 && p.K <= 128)) && p.M >= 4096) {
+        // wide GEGLU projections at K >= 640 and the 128-channel VAE convs: 256 x 128 tile on 4 waves (wave tile 128 x 64, 32 MFMAs per barrier,
+        // 25 % fewer LDS-fill bytes per flop), BK 32 x 3 stages: 72 KiB -> 2 blocks / CU (lin_L1_ff1_geglu 662 -> 779, lin_L2_ff1_geglu 708 -> 865 TF/s)
+        p.mt = (int)((p.M + 255) / 256);
+        const dim3 g2((unsigned)(p.mt * p.nt), (unsigned)batch, 1);
+        V3D_LAUNCH(2, 256, 128, (long long)g2.x * g2.y, (gemm_kernel_v2<256, 128, 2, 2, 3, 1, MODE, GEGLU>), g2, 256, st, p);
+    } else if ((long long)ntaps<MODE>() * ((p.K + 31) / 32) <= 40) {
+        // measured on MI355X (profiles/r01_gemm_sweep.txt): short contractions (<= 40 stages of 32: every K <= 1280 linear, the 128-channel
+        // VAE convs) are bound by per-tile fill/drain bubbles -> more co-resident blocks: BK 32 x 3 stages, 48 KiB LDS, 3 blocks / CU
+        V3D_LAUNCH(2, BM, BN, (long long)grid.x * grid.y, (gemm_kernel_v2<BM, BN, 2, 2, 3, 1, MODE, GEGLU>), grid, 256, st, p);
+    } else if (p.K % 64 == 0) {
+        // long contractions prefer fewer barriers per MFMA: BK 64 x 2 stages (one in flight)
+        V3D_LAUNCH(2, BM, BN, (long long)grid.x * grid.y, (gemm_kernel_v2<BM, BN, 2, 2, 2, 2, MODE, GEGLU>), grid, 256, st, p);
+    } else {
+        V3D_LAUNCH(2, BM, BN, (long long)grid.x * grid.y, (gemm_kernel_v2<BM, BN, 2, 2, 4, 1, MODE, GEGLU>), grid, 256, st, p);   // BK 32 x 4 stages
     }
-    if (p.K % 64 != 0 && (cfg == 1 || cfg == 4 || cfg == 7 || cfg == 9)) cfg = (cfg == 4) ? 3 : (cfg == 9 ? 8 : 0);   // BK 64 stages need K % 64 == 0
-    switch (cfg) {
-        case 1:   // BK 64 stages, 2 deep (one in flight)
-            V3D_LAUNCH(2, BM, BN, (long long)grid.x * grid.y, (gemm_kernel_v2<BM, BN, 2, 2, 2, 2, MODE, GEGLU>), grid, 256, st, p);
-            break;
-        case 2:   // BK 32 stages, 3 deep: 3 blocks / CU
-            V3D_LAUNCH(2, BM, BN, (long long)grid.x * grid.y, (gemm_kernel_v2<BM, BN, 2, 2, 3, 1, MODE, GEGLU>), grid, 256, st, p);
-            break;
-        case 3:   // 256 x 128 tile, 8 waves (4 x 2), BK 32 x 4 stages (N tiles of 64 keep the 4-wave kernel)
-        case 4:   // 256 x 128 tile, 8 waves, BK 64 x 3 stages
-            if constexpr (BN == 128) {
-                p.mt = (int)((p.M + 255) / 256);
-                dim3 g2((unsigned)(p.mt * p.nt), (unsigned)batch, 1);
-                if (cfg == 3)
-                    V3D_LAUNCH(2, 256, BN, (long long)g2.x * g2.y, (gemm_kernel_v2<256, BN, 4, 2, 4, 1, MODE, GEGLU>), g2, 512, st, p);
-                else
-                    V3D_LAUNCH(2, 256, BN, (long long)g2.x * g2.y, (gemm_kernel_v2<256, BN, 4, 2, 3, 2, MODE, GEGLU>), g2, 512, st, p);
-                break;
-            }
-            [[fallthrough]];
-        case 11:  // 256 x 128 tile on 4 waves (wave tile 128 x 64, 32 MFMAs per barrier), BK 32 x 3: 72 KiB -> 2 blocks / CU
-            if constexpr (BN == 128) {
-                p.mt = (int)((p.M + 255) / 256);
-                dim3 g2((unsigned)(p.mt * p.nt), (unsigned)batch, 1);
-                V3D_LAUNCH(2, 256, 128, (long long)g2.x * g2.y, (gemm_kernel_v2<256, 128, 2, 2, 3, 1, MODE, GEGLU>), g2, 256, st, p);
-                break;
-            }
-            [[fallthrough]];
-        case 10:  // BK 32 stages, 2 deep: 32 KiB LDS -> 4 blocks / CU (VGPR-limited)
-            V3D_LAUNCH(2, BM, BN, (long long)grid.x * grid.y, (gemm_kernel_v2<BM, BN, 2, 2, 2, 1, MODE, GEGLU>), grid, 256, st, p);
-            break;
-        case 7:   // BK 64 stages, 3 deep
-            V3D_LAUNCH(2, BM, BN, (long long)grid.x * grid.y, (gemm_kernel_v2<BM, BN, 2, 2, 3, 2, MODE, GEGLU>), grid, 256, st, p);
-            break;
-        case 8:   // 256 x 64 tile, 4 waves stacked along M (wave tile 64 x 64), BK 32 x 3
-        case 9:   // 256 x 64 tile, 4 waves, BK 64 x 2
-            if constexpr (BN == 64) {
-                p.mt = (int)((p.M + 255) / 256);
-                dim3 g2((unsigned)(p.mt * p.nt), (unsigned)batch, 1);
-                if (cfg == 8)
-                    V3D_LAUNCH(2, 256, 64, (long long)g2.x * g2.y, (gemm_kernel_v2<256, 64, 4, 1, 3, 1, MODE, GEGLU>), g2, 256, st, p);
-                else
-                    V3D_LAUNCH(2, 256, 64, (long long)g2.x * g2.y, (gemm_kernel_v2<256, 64, 4, 1, 2, 2, MODE, GEGLU>), g2, 256, st, p);
-                break;
-            }
-            [[fallthrough]];
-        default:  // cfg 0: BK 32 stages, 4 deep
-            V3D_LAUNCH(2, BM, BN, (long long)grid.x * grid.y, (gemm_kernel_v2<BM, BN, 2, 2, 4, 1, MODE, GEGLU>), grid, 256, st, p);
-    }
-    return v3d_check_launch("v3d_gemm");
-}
-
-template <int MODE, bool GEGLU>
-int launch256(const GP& p0, int batch, hipStream_t st, int cfg) {
-    GP p = p0;
-    p.mt = (int)((p.M + 255) / 256);
-    p.nt = (int)((p.N + 255) / 256);
-    dim3 grid((unsigned)(p.mt * p.nt), (unsigned)batch, 1);
-    if (cfg == 5)
-        V3D_LAUNCH(2, 256, 256, (long long)grid.x * grid.y, (gemm_kernel_v2<256, 256, 4, 2, 3, 1, MODE, GEGLU>), grid, 512, st, p);
-    else
-        V3D_LAUNCH(2, 256, 256, (long long)grid.x * grid.y, (gemm_kernel_v2<256, 256, 4, 2, 2, 2, MODE, GEGLU>), grid, 512, st, p);
     return v3d_check_launch("v3d_gemm");
 }
 
@@ -994,25 +873,17 @@ thread_local bool g_gn_in_epilogue = false;
 long long g_gn_epilogue_launches = 0;      // (tests: how many launches of this process gathered the statistics in their epilogue)
 
 template <int MODE, bool GEGLU>
-int launch_v3(const GP& p0, hipStream_t st, int variant, long long m_off = 0, long long m_rows = -1) {
+int launch_v3(const GP& p0, hipStream_t st, int variant) {
     GP p = p0;
     const int bm = variant == 1 ? 192 : 256, bn = variant == 1 ? 320 : (variant == 2 ? 128 : 256);
-    p.m_off = m_off;                                        // (split launches: rows [m_off, m_off + m_rows) of the operation)
-    p.mt = (int)(((m_rows > 0 ? m_rows : p.M) + bm - 1) / bm);
+    p.mt = (int)((p.M + bm - 1) / bm);
     p.nt = (int)((p.N + bn - 1) / bn);
     const int ntiles = p.mt * p.nt;
     const int grid = ntiles < v3d_num_cus() ? ntiles : v3d_num_cus();
-    if constexpr (MODE == V3D_GEMM_LINEAR && !GEGLU) {
-        if V3D_ABL(p, 8) {
-            if (variant == 1) V3D_LAUNCH(3, 192, 320, ntiles, (gemm_kernel_v3<192, 320, 2, 4, MODE, GEGLU, 1, true>), dim3(grid), 512, st, p, ntiles);
-            else V3D_LAUNCH(3, 256, 256, ntiles, (gemm_kernel_v3<256, 256, 2, 4, MODE, GEGLU, 1, true>), dim3(grid), 512, st, p, ntiles);
-            return v3d_check_launch("v3d_gemm");
-        }
-    }
     if constexpr (GEGLU && MODE == V3D_GEMM_LINEAR) {
         if (variant == 2) {   // epilogue-bound GEGLU projections (K = 320): 256 x 128 tile, two blocks per CU
             const int g2 = ntiles < 2 * v3d_num_cus() ? ntiles : 2 * v3d_num_cus();
-            V3D_LAUNCH(3, 256, 128, ntiles, (gemm_kernel_v3<256, 128, 4, 2, MODE, GEGLU, 1, false, 3, 0>), dim3(g2), 512, st, p, ntiles);
+            V3D_LAUNCH(3, 256, 128, ntiles, (gemm_kernel_v3<256, 128, 4, 2, MODE, GEGLU, 1, 3, 0>), dim3(g2), 512, st, p, ntiles);
             return v3d_check_launch("v3d_gemm");
         }
     }
@@ -1023,7 +894,7 @@ int launch_v3(const GP& p0, hipStream_t st, int variant, long long m_off = 0, lo
             if (p.gn_stats && 80 % p.gn_cpg == 0 && p.gn_nslots >= p.gn_rps / 96 + 2) {
                 g_gn_in_epilogue = true;
                 ++g_gn_epilogue_launches;
-                V3D_LAUNCH(3, 192, 320, ntiles, (gemm_kernel_v3<192, 320, 2, 4, MODE, GEGLU, 1, false, 4, 16, true>), dim3(grid), 512, st, p, ntiles);
+                V3D_LAUNCH(3, 192, 320, ntiles, (gemm_kernel_v3<192, 320, 2, 4, MODE, GEGLU, 1, 4, 16, true>), dim3(grid), 512, st, p, ntiles);
             } else {
                 V3D_LAUNCH(3, 192, 320, ntiles, (gemm_kernel_v3<192, 320, 2, 4, MODE, GEGLU, 1>), dim3(grid), 512, st, p, ntiles);
             }
@@ -1032,7 +903,7 @@ int launch_v3(const GP& p0, hipStream_t st, int variant, long long m_off = 0, lo
         if (p.gn_stats && variant == 0 && 64 % p.gn_cpg == 0 && p.gn_nslots >= p.gn_rps / 128 + 2) {
             g_gn_in_epilogue = true;
             ++g_gn_epilogue_launches;
-            V3D_LAUNCH(3, 256, 256, ntiles, (gemm_kernel_v3<256, 256, 2, 4, MODE, GEGLU, 1, false, 4, 16, true>), dim3(grid), 512, st, p, ntiles);
+            V3D_LAUNCH(3, 256, 256, ntiles, (gemm_kernel_v3<256, 256, 2, 4, MODE, GEGLU, 1, 4, 16, true>), dim3(grid), 512, st, p, ntiles);
             return v3d_check_launch("v3d_gemm");
         }
     }
@@ -1041,7 +912,7 @@ int launch_v3(const GP& p0, hipStream_t st, int variant, long long m_off = 0, lo
         // 128-byte lines of every output row (the 2 x 4 layout wrote 64-byte half lines from two different waves)
         // measured (tools/gemm_floor.py, M = 147456, N = 2560): K = 320: 396 us vs 416 us (2 x 4) vs 402 us (two 256 x 128 blocks
         // per CU) vs 421 us (v2); at K >= 640 the 2 x 4 layout with 32-row chunks is ahead again (tools/gemm_sweep.py)
-        if (p.K < 640 && !V3D_ABL(p, 128)) {
+        if (p.K < 640) {
             V3D_LAUNCH(3, 256, 256, ntiles, (gemm_kernel_v3<256, 256, 4, 2, MODE, GEGLU, 1>), dim3(grid), 512, st, p, ntiles);
             return v3d_check_launch("v3d_gemm");
         }
@@ -1056,7 +927,7 @@ int v6_choice() {
     static int v = -1;
     if (v < 0) {
         const char* e = getenv("V3D_GEMM_V6");
-        v = e ? atoi(e) : V3D_GEMM_V6_DEFAULT;
+        v = e ? atoi(e) : 1;
     }
     return v;
 }
@@ -1084,7 +955,7 @@ int launch_v6(const GP& p0, hipStream_t st) {
 template <int MODE>
 int try_v6(const GP& p, hipStream_t st) {
     const int v6 = v6_choice();
-    if (!v6 || impl_choice() != 0 || cfg_choice() >= 0 || p.K % 32 || p.K * 2 > 65536 || p.M % 192 || p.N % 160 || p.gn_stats || !e4_ok(p, 96, 80)) return -1;
+    if (!v6 || impl_choice() != 0 || p.K % 32 || p.K * 2 > 65536 || p.M % 192 || p.N % 160 || p.gn_stats || !e4_ok(p, 96, 80)) return -1;
     const long long cus = v3d_num_cus(), slots = 2 * cus;
     const bool v1 = p.N % 320 == 0;
     const long long bm = v1 ? 192 : 256, bn = v1 ? 320 : 256;
@@ -1097,16 +968,6 @@ int try_v6(const GP& p, hipStream_t st) {
 
 template <int MODE, bool GEGLU>
 int dispatch(const GP& p, int batch, hipStream_t st) {
-#ifdef V3D_EXPERIMENTS
-    if constexpr (MODE == V3D_GEMM_LINEAR && !GEGLU) {
-        static int v7 = -1;
-        if (v7 < 0) {
-            const char* e = getenv("V3D_GEMM_V7");
-            v7 = e ? atoi(e) : 0;
-        }
-        if (v7 && batch == 1 && v3d_gemm_v7_variant(p, MODE)) return v3d_gemm_v7_launch(p, (void*)st);
-    }
-#endif
     if constexpr ((MODE == V3D_GEMM_LINEAR || MODE == V3D_GEMM_CONVT3) && !GEGLU) {
         if (batch == 1) {
             const int rc = try_v6<MODE>(p, st);
@@ -1114,7 +975,7 @@ int dispatch(const GP& p, int batch, hipStream_t st) {
         }
     }
     // v3 (persistent big tiles) unless forced off (V3D_GEMM_IMPL=1/2), forced on (=3), or the tile count fills the CUs badly
-    if (impl_choice() != 1 && impl_choice() != 2 && cfg_choice() < 0 && batch == 1 && p.K % 32 == 0 && p.K * 2 <= 65536 && p.N >= 256) {
+    if (impl_choice() != 1 && impl_choice() != 2 && batch == 1 && p.K % 32 == 0 && p.K * 2 <= 65536 && p.N >= 256) {
         const int variant = (!GEGLU && p.N % 320 == 0) ? 1 : 0;
         const long long bm = variant ? 192 : 256, bn = variant ? 320 : 256;
         const long long nt3 = ((p.M + bm - 1) / bm) * ((p.N + bn - 1) / bn), cus = v3d_num_cus();
@@ -1126,44 +987,13 @@ int dispatch(const GP& p, int batch, hipStream_t st) {
         // measured (profiles/r01f_op_times_v3.txt): v3 wins wherever its tiles fill the CUs about as well as v2's do
         if (GEGLU && (p.K < 640 || v3s_choice() >= 2) && v3s_choice() && v3_ok(p, 64, 64) && ((p.M + 255) / 256) * ((p.N + 127) / 128) >= 2 * cus)
             return launch_v3<MODE, GEGLU>(p, st, 2);
-        static double fill_k = -1.0;
-        if (fill_k < 0) {
-            const char* e = getenv("V3D_GEMM_FILL");   // tuning knob
-            fill_k = e ? atof(e) : 0.9;
-        }
-        const bool want = impl_choice() == 3 || fill3 >= fill_k * fill2;
+        const bool want = impl_choice() == 3 || fill3 >= 0.9 * fill2;
         // (non-GEGLU v3 kernels only carry the hand-managed epilogue: its operand contract on top of the tile-shape one)
         const bool eok = GEGLU || (variant ? e4_ok(p, 96, 80) : e4_ok(p, 128, 64));
         if (want && eok && (variant ? v3_ok(p, 96, 80) : v3_ok(p, 128, 128))) {
-#ifdef V3D_EXPERIMENTS
-            if constexpr (!GEGLU) {
-                // lab only (tools/lab/gemm4.hip, linked into the experiments library): the one-wave-per-SIMD kernels of round 4, V3D_GEMM_V4=1
-                static int v4 = -1;
-                if (v4 < 0) {
-                    const char* e = getenv("V3D_GEMM_V4");
-                    v4 = e ? atoi(e) : 0;
-                }
-                static int v5 = -1;
-                if (v5 < 0) {
-                    const char* e = getenv("V3D_GEMM_V5");
-                    v5 = e ? atoi(e) : 0;
-                }
-                const int v5v = v5 ? v3d_gemm_v5_variant(p, MODE, variant) : 0;
-                if (v5v) return v3d_gemm_v5_launch(p, MODE, v5v, (void*)st);
-                const int v4v = v4 ? v3d_gemm_v4_variant(p, MODE, variant) : 0;
-                if (v4v) {
-                    if (p.gn_stats) {
-                        g_gn_in_epilogue = true;
-                        ++g_gn_epilogue_launches;
-                    }
-                    return v3d_gemm_v4_launch(p, MODE, v4v, (void*)st);
-                }
-            }
-#endif
             return launch_v3<MODE, GEGLU>(p, st, variant);
         }
     }
-    if ((cfg_choice() == 5 || cfg_choice() == 6) && impl_choice() != 1 && p.N % 256 == 0 && p.K % 64 == 0 && p.K * 2 <= 65536) return launch256<MODE, GEGLU>(p, batch, st, cfg_choice());
     // N tile: 128 unless a 64-wide tile wastes less (e.g. N = 320: 5 x 64 exact vs 3 x 128 = 17 % padding)
     const long long w128 = ((p.N + 127) / 128) * 128, w64 = ((p.N + 63) / 64) * 64;
     // (64-row tiles for the small-M 8x8 level were measured slower than under-filled 128-row tiles: conv_L3 461 vs 586 TF/s)
@@ -1279,11 +1109,6 @@ extern "C" long long v3d_debug_sk_timeouts(void) {
     return t;
 }
 
-// experiments only (not part of the ABI header): copy the v3 slot timeline out
-extern "C" int v3d_debug_v3_timeline(unsigned long long* host_out) {
-    return hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_v3_dbg), sizeof(g_v3_dbg)) == hipSuccess ? 0 : -1;
-}
-
 namespace {
 int run_mode(const v3d_gemm_args* a, GP& p, hipStream_t st);
 }
@@ -1326,21 +1151,10 @@ int fill_params(const v3d_gemm_args* a, GP& p, int* halo) {
     p.halo_rows = a->mode == V3D_GEMM_CONVT3 ? a->halo_rows : 0;
     p.sA = a->sA; p.sW = a->sW; p.sO = a->sO;
     p.mt = p.nt = 0;
-    p.m_off = 0;
-    {
-        static int gm = -2, ti = -2;
-        if (gm == -2) { const char* e = getenv("V3D_GEMM_GROUPM"); gm = e ? atoi(e) : -1; }      // -1 = heuristic, 0 / 1 = row-major walk, n = groups of n tile rows
-        if (ti == -2) { const char* e = getenv("V3D_GEMM_TAPINNER"); ti = e ? atoi(e) : -1; }
-        p.group_m = gm;        // (-1: resolved per launch from the tile-row count, see launch_group_m)
-        p.tap_inner = ti < 0 ? V3D_GEMM_TAPINNER_DEFAULT : ti;
-    }
+    p.group_m = -1;        // tile walk: the heuristic of tile_coords (v6 sets its own)
     p.split_n = 1;
     p.ws = nullptr;
-    p.ablate = 0;
     p.sk_tail = p.sk_full = p.sk_units = 0; p.sk_ws = nullptr; p.sk_flags = nullptr;
-#ifdef V3D_EXPERIMENTS
-    { static int ab = -1; if (ab < 0) { const char* e = getenv("V3D_GEMM_ABLATE"); ab = e ? atoi(e) : 0; } p.ablate = ab; }
-#endif
     p.gn_stats = nullptr; p.gn_rps = 0; p.gn_cpg = 0; p.gn_nslots = 0;
     if (a->gn_stats) {
         V3D_REQUIRE(!a->geglu && !a->out_fp32 && a->batch == 1, "v3d_gemm: gn_stats needs a bf16, non-GEGLU, unbatched output");
@@ -1348,9 +1162,7 @@ int fill_params(const v3d_gemm_args* a, GP& p, int* halo) {
         V3D_REQUIRE(a->gn_rps >= 16 && a->gn_rps % 16 == 0 && a->gn_rps < (1ll << 30) && a->M % a->gn_rps == 0, "v3d_gemm: gn_rps must be a multiple of 16 that divides M");
         V3D_REQUIRE(a->ldo == a->N && ((uintptr_t)a->gn_stats & 7) == 0, "v3d_gemm: gn_stats needs a dense output (ldo == N) and an 8-byte aligned buffer");
         V3D_REQUIRE(a->gn_nslots >= 1, "v3d_gemm: gn_nslots must be >= 1");
-        static int ep = -1;
-        if (ep < 0) { const char* e = getenv("V3D_GEMM_GN_EPILOGUE"); ep = e ? atoi(e) : 1; }      // A/B knob: 0 = always the stand-alone statistics kernel
-        if (ep) { p.gn_stats = a->gn_stats; p.gn_rps = a->gn_rps; p.gn_cpg = a->gn_cpg; p.gn_nslots = a->gn_nslots; }
+        p.gn_stats = a->gn_stats; p.gn_rps = a->gn_rps; p.gn_cpg = a->gn_cpg; p.gn_nslots = a->gn_nslots;
     }
     // GroupNorm (+SiLU) of the input in the operand path / two-source input: only the LDS-haloed kernels (conv.hip) take these
     p.A2 = (const bf16_t*)a->A2; p.K1 = a->A2 ? a->K1 : a->K; p.lda2 = a->lda2; p.a2_bytes = 0;
@@ -1372,9 +1184,7 @@ int fill_params(const v3d_gemm_args* a, GP& p, int* halo) {
         p.upshift = a->up - 1;
         p.pad_lo = a->pad_mode ? 0 : 1;
     }
-    static int hk = -1;
-    if (hk < 0) { const char* e = getenv("V3D_CONV_HALO"); hk = e ? atoi(e) : 1; }     // A/B knob: 0 = never, 1 = launches with gn_in_table (default), 2 = every launch of a fitting shape
-    if (a->batch == 1 && !a->geglu && (a->mode == V3D_GEMM_CONV3X3 || a->mode == V3D_GEMM_CONVT3) && ((hk == 1 && a->gn_in_table) || hk >= 2))
+    if (a->gn_in_table && a->batch == 1 && !a->geglu && (a->mode == V3D_GEMM_CONV3X3 || a->mode == V3D_GEMM_CONVT3))
         *halo = v3d_conv_halo_variant(p, a->mode);
     return V3D_OK;
 }
@@ -1393,15 +1203,10 @@ extern "C" int v3d_gemm(const v3d_gemm_args* a, v3d_stream_t stream) {
     const int frc = fill_params(a, p, &halo);
     if (frc != V3D_OK) return frc;
     hipStream_t st = (hipStream_t)stream;
-    if (halo) {
-        const int rc = v3d_conv_halo_launch(p, halo, stream);     // (its epilogue gathers gn_stats itself ...
-        // ... unless the A/B knob V3D_GEMM_GN_EPILOGUE=0 took the request out of the parameter block: then the stand-alone pass runs here too)
-        if (rc != V3D_OK || !a->gn_stats || p.gn_stats) return rc;
-        return v3d_groupnorm_stats(a->out, a->N, nullptr, 0, a->gn_stats, a->gn_nslots, a->M / a->gn_rps, a->gn_rps, 32, 1, stream);
-    }
+    if (halo) return v3d_conv_halo_launch(p, halo, stream);      // (its epilogue gathers gn_stats itself)
     V3D_REQUIRE(!a->gn_in_table, "v3d_gemm: gn_in_table is set but this shape is not one of the LDS-haloed kernels' (v3d_gemm_gn_in_supported): "
                                  "normalise the input with v3d_groupnorm_apply first");
-    if (p.gn_stats || a->gn_stats) {
+    if (p.gn_stats) {
         g_gn_in_epilogue = false;
         const int rc = run_mode(a, p, st);
         if (rc != V3D_OK || g_gn_in_epilogue) return rc;

@@ -12,16 +12,6 @@
 #define E4_ASM_READS 1
 #endif
 
-// Experiment switches (skip epilogue / MFMAs / DMA / stores, slot timelines) exist only in builds made with -DV3D_EXPERIMENTS
-// (tools/gemm_floor.py, tools/v3_timeline.py say how); the shipped library has no environment variable that changes results.
-#ifdef V3D_EXPERIMENTS
-#define V3D_ABL(p, bit) ((p).ablate & (bit))
-#elif defined(V3D_ABL_STATIC)      // A/B builds only (tools/build_variant.sh <tag> "-DV3D_ABL_STATIC=<bits>"): the same switches at compile time - no branch in the measured code
-#define V3D_ABL(p, bit) ((V3D_ABL_STATIC) & (bit))
-#else
-#define V3D_ABL(p, bit) (0)
-#endif
-
 struct V3dGemmParams {
     const bf16_t* A;
     const bf16_t* W;
@@ -43,14 +33,11 @@ struct V3dGemmParams {
     int T, tmin, tmax;
     long long S;
     long long halo_rows; // CONVT3 split-halo layout (0 = dense)
-    long long m_off;     // first output row of this launch (a launch over the row range [m_off, m_off + mt * BM) of the operation: gemm.hip split launches); M stays the operation's
     long long sA, sW, sO;
     int mt, nt;  // tile counts
-    int group_m;         // tile walk: > 1 = ids run down groups of `group_m` tile rows first (L2-friendly patches), else row-major over N
-    int tap_inner;       // multi-tap modes: 1 = stage order (k outer, tap inner): the taps re-read an activation tile while it is still in L2
+    int group_m;         // tile walk: < 0 = the heuristic of tile_coords, > 1 = ids run down groups of `group_m` tile rows first (L2-friendly patches), else row-major over N
     int split_n;         // > 1: split-K launch: blockIdx.y = split index = output slab (out = fp32 workspace [split][M][N], plain stores)
     const float* ws;     // finalize kernel only: the workspace to reduce
-    int ablate;  // experiments only (env V3D_GEMM_ABLATE): 1 = no output stores, 2 = no MFMAs, 4 = no LDS-DMA loads
     float* gn_stats;     // GroupNorm partial sums of the output [M / gn_rps][gn_nslots][32][2], stored by the <GN> epilogues (else NULL)
     long long gn_rps;    // rows per statistics group
     long long gn_nslots; // slots per statistics group; a writer (wave tile x statistics group) owns slot ceil(first row in group / wave-tile rows)
@@ -81,18 +68,6 @@ void v3d_note_launch(int family, int bm, int bn, long long tiles, int blocks_per
 // conv.hip: the LDS-haloed kernels (GroupNorm + SiLU in the operand path)
 int v3d_conv_halo_variant(const V3dGemmParams& p, int mode);          // 0 = not one of their shapes
 int v3d_conv_halo_launch(const V3dGemmParams& p, int variant, void* stream);
-#ifdef V3D_EXPERIMENTS
-// tools/lab/gemm4.hip (experiments library only): the one-wave-per-SIMD persistent kernels of round 4 (0 = not one of their launches, else the
-// variant: 1 = 192 x 320 tiles, 2 = 256 x 256).  5 % slower than v3 (NOTES 11.2): kept as a lab record, not part of the product library.
-int v3d_gemm_v4_variant(const V3dGemmParams& p, int mode, int v3_variant);
-int v3d_gemm_v4_launch(const V3dGemmParams& p, int mode, int variant, void* stream);
-// tools/lab/gemm5.hip: the same structure on v_mfma_f32_32x32x16_bf16 (round 6, V3D_GEMM_V5=1)
-int v3d_gemm_v5_variant(const V3dGemmParams& p, int mode, int v3_variant);
-int v3d_gemm_v5_launch(const V3dGemmParams& p, int mode, int variant, void* stream);
-// tools/lab/gemm7.hip: N = 320, K = 320 / 640 linears with a deferred epilogue (round 6, V3D_GEMM_V7=1)
-int v3d_gemm_v7_variant(const V3dGemmParams& p, int mode);
-int v3d_gemm_v7_launch(const V3dGemmParams& p, void* stream);
-#endif
 // gemm.hip: stream-K plan of a persistent launch (fills p.sk_*, returns the grid): ntiles tiles of `units` split granules on the device's CUs;
 // slot_bytes = one block's accumulators in fp32.  Leaves the classic assignment (sk_tail = 0) when the tail round is full enough or too thin.
 int v3d_sk_plan(V3dGemmParams& p, int ntiles, int units, int min_units, int min_saved, size_t slot_bytes, void* stream);
@@ -198,7 +173,7 @@ __device__ __forceinline__ int xcd_remap(int bid, int nblk) {
 // the N = 10240 GEGLU projection fetched 20x its algorithmic bytes).  group_m > 1 walks down `group_m` tile rows before moving to the next
 // tile column, so the concurrent set is a group_m x (concurrency / group_m) patch that shares both operands; bijective for any mt, nt.
 __device__ __forceinline__ void tile_coords(const GP& p, int id, int& tm, int& tn) {
-    const int gm = p.group_m >= 0 ? p.group_m : (p.mt >= 96 ? 8 : 4);     // < 0: heuristic (see the knob comment at the top)
+    const int gm = p.group_m >= 0 ? p.group_m : (p.mt >= 96 ? 8 : 4);     // < 0: heuristic (measurements at the top of gemm.hip)
     if (gm <= 1 || p.nt == 1) {
         tn = id % p.nt;
         tm = id / p.nt;
@@ -328,15 +303,6 @@ template <int MF, int NF, bool GEGLU, bool CAN_STAGE, bool FAST_ONLY = false, in
 __device__ __forceinline__ void epilogue(const GP& p, f32x4 (&acc)[MF][NF], long long mw0, long long nw0, long long z, int lane,
                                          unsigned char* stage, u32x4 pre0, u32x4 pre1, u32x4 pre2, bool res_pre,
                                          const float4 (&bias_pre)[NF], bool has_bias_pre, GnAcc<GN ? NF : 1>* gn = nullptr) {
-    if V3D_ABL(p, 1) {
-        float sum = 0.f;
-#pragma unroll
-        for (int i = 0; i < MF; ++i)
-#pragma unroll
-            for (int j = 0; j < NF; ++j) sum += acc[i][j][0] + acc[i][j][1] + acc[i][j][2] + acc[i][j][3];
-        if (sum == 123.456f) reinterpret_cast<float*>(p.out)[0] = sum;   // keeps the accumulators live
-        return;
-    }
     const long long Nout = GEGLU ? p.N / 2 : p.N;
     constexpr int NFO = GEGLU ? NF / 2 : NF;          // output fragments per wave-tile row
     constexpr int SROW = NFO * 32 + SPAD;             // staging row stride in bytes (16 B pad unless LDS is too tight)
@@ -420,7 +386,7 @@ __device__ __forceinline__ void epilogue(const GP& p, f32x4 (&acc)[MF][NF], long
                         g[0] += a.x; g[1] += a.y; g[2] += a.z; g[3] += a.w;
                     }
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) v[r] = V3D_ABL(p, 16) ? v[r] * g[r] : geglu_mul(v[r], g[r]);
+                    for (int r = 0; r < 4; ++r) v[r] = geglu_mul(v[r], g[r]);
                     (void)dummy;
                 }
                 const int jo = GEGLU ? (j >> 1) : j;
@@ -459,7 +425,7 @@ __device__ __forceinline__ void epilogue(const GP& p, f32x4 (&acc)[MF][NF], long
             for (int c0 = 0; c0 < ROWS * CPRO; c0 += 64) {
                 const int c = c0 + lane;
                 const int row = c / CPRO, ch = c % CPRO;
-                if ((WHOLE || c < ROWS * CPRO) && !V3D_ABL(p, 32)) *reinterpret_cast<uint4*>(outz + (long long)row * p.ldo + ch * 8) = *reinterpret_cast<const uint4*>(stage + row * SROW + ch * 16);
+                if (WHOLE || c < ROWS * CPRO) *reinterpret_cast<uint4*>(outz + (long long)row * p.ldo + ch * 8) = *reinterpret_cast<const uint4*>(stage + row * SROW + ch * 16);
             }
         }
         return;
@@ -776,7 +742,7 @@ __device__ __forceinline__ void e4_fragment(const GP& p, f32x4 (&acc)[NF], long 
         e4_lds_read16(sr, sbase + (unsigned)((cr / CPRO) * SROW + (cr % CPRO) * 16));
         asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(sr)::"memory");
         const int row = c / CPRO, ch = c % CPRO;
-        if ((NP % 64 == 0 || c < NP) && !V3D_ABL(p, 1)) *reinterpret_cast<u32x4*>(outz + (long long)row * p.ldo + ch * 8) = sr;
+        if (NP % 64 == 0 || c < NP) *reinterpret_cast<u32x4*>(outz + (long long)row * p.ldo + ch * 8) = sr;
     }
     } else {
     // (RD = 0: compiler-visible reads, each behind the compiler's vmcnt(0) - the 3 x 3 LDS-haloed kernels of conv.hip: their tiles are 90-360 steps long and the asm forms measured +-1 %)
@@ -806,33 +772,20 @@ __device__ __forceinline__ void e4_fragment(const GP& p, f32x4 (&acc)[NF], long 
     for (int k = 0; k < (NP + 63) / 64; ++k) {
         const int c = k * 64 + lane;
         const int row = c / CPRO, ch = c % CPRO;
-        if ((NP % 64 == 0 || c < NP) && !V3D_ABL(p, 1)) *reinterpret_cast<uint4*>(outz + (long long)row * p.ldo + ch * 8) = *reinterpret_cast<const uint4*>(stage + row * SROW + ch * 16);
+        if (NP % 64 == 0 || c < NP) *reinterpret_cast<uint4*>(outz + (long long)row * p.ldo + ch * 8) = *reinterpret_cast<const uint4*>(stage + row * SROW + ch * 16);
     }
     }
 }
 
-// Residual pieces run E4_DEPTH fragments ahead of their use (round 3: one fragment, waited for together with the previous fragment's stores).
-// A fragment's arithmetic is ~0.2 us, a loaded memory round trip 1-2 us: with the pieces of three fragments in flight (36 registers - the
-// main loop's operand fragments are dead here) the wave pays the latency once per tile, in the constants' wait, not once per fragment.
-#ifndef E4_DEPTH
-#define E4_DEPTH 1
-#endif
-// the LINEAR v3 kernels have the registers for a deeper look-ahead (248-254 VGPRs, no spills at depth 2 / 3; the multi-tap loaders spill: depth 1)
-#ifndef E4_DEPTH_LINEAR
-#define E4_DEPTH_LINEAR 1
-#endif
-// (v6 ran depth 2 while the compiler's drains were in place: -2 % then; with the asm staging reads depth 1 measures the same or 1-3 % better per launch and
-// keeps one set of in-flight registers less in rotation - profiles/r06_e4_asm_reads_ab.txt)
-#ifndef E4_DEPTH_V6
-#define E4_DEPTH_V6 1
-#endif
+// Residual pieces run one fragment ahead of their use (round 3: waited for together with the previous fragment's stores; deeper look-ahead
+// was measured and dropped in round 6, profiles/r06_e4_asm_reads_ab.txt).
 template <int NF>
 struct E4Cnt {
     static constexpr int NP = 16 * NF * 2;
     static constexpr int LOADS = NP > 128 ? 3 : 2;       // asm loads per fragment (e4_load_res)
     static constexpr int STORES = (NP + 63) / 64;        // 16-byte row stores per fragment (e4_fragment)
 };
-// GroupNorm-statistics writer bookkeeping of a wave tile whose fragments are CONSECUTIVE 16-row runs (v3 / v4 kernels, the 3x3 haloed kernel): the
+// GroupNorm-statistics writer bookkeeping of a wave tile whose fragments are CONSECUTIVE 16-row runs (v3 kernels, the 3x3 haloed kernel): the
 // statistics group of the current fragment and its first row inside it, advanced per fragment (called once per fragment, in order).  A writer
 // = the wave tile's run of rows inside one statistics group; slot = ceil(first row of the run inside the group / wave-tile rows).
 template <int WMR, int MF>
@@ -859,36 +812,23 @@ struct E4GnRun {
 };
 // retire the MF fragments of a finished wave tile; RowFn(f) = first output row of fragment f, FlushFn(f, m0f, slot&, sid&) = flush? of the
 // GroupNorm-statistics epilogue.  Residual pieces travel by value (a reference went through a stack array, see conv.hip halo_retire):
-// cur / n1 / n2 = the pieces of fragments F, F + 1, F + 2 (as far as E4_DEPTH reaches; the rest are dead values).
-// accumulator source: get<F>(out) hands over the NF fragments of row fragment F.  Register-array form (v3 kernels, conv.hip):
-template <int MF, int NF>
-struct E4AccArray {
-    f32x4 (&a)[MF][NF];
-    template <int F>
-    __device__ __forceinline__ void get(f32x4 (&out)[NF]) const {
-#pragma unroll
-        for (int j = 0; j < NF; ++j) out[j] = a[F][j];
-    }
-};
-template <int F, int MF, int NF, bool GN, int D, int RD, typename Acc, typename RowFn, typename FlushFn>
-__device__ __forceinline__ void e4_retire(const GP& p, const Acc& acc, long long nw0, int lane, unsigned char* stage, E4Res cur, E4Res n1, E4Res n2,
+// cur = the pieces of fragment F, n1 = where those of fragment F + 1 are loaded.  n2 is a spare set that is never loaded: it is what n1 holds
+// without a residual, and the register barriers (asm statements) name it.  Dropping it moves the register allocation of the in-flight pieces,
+// and tools/check_inflight_regs.py then finds v_mov copies of registers whose asm load is still in flight (v6 temporal kernel).
+template <int F, int MF, int NF, bool GN, int RD, typename RowFn, typename FlushFn>
+__device__ __forceinline__ void e4_retire(const GP& p, f32x4 (&acc)[MF][NF], long long nw0, int lane, unsigned char* stage, E4Res cur, E4Res n1, E4Res n2,
                                           E4Tile<NF> t, GnAcc<GN ? NF : 1>& gn, RowFn rowfn, FlushFn flushfn) {
     if constexpr (F < MF) {
-        static_assert(D >= 1 && D <= 3, "residual look-ahead: 1..3 fragments");
-        // depth 3 needs the compiler-visible reads (RD = 0): without their drains the register allocator's copies of the rotating piece sets (cur <- n1 <- n2 <- n3) read
-        // registers whose asm load is still in flight - wrong results in profiles/r06_e4_asm_reads_ab.txt, found by tools/check_inflight_regs.py; depths 1 and 2 are clean
-        static_assert(D <= 2 || RD == 0, "e4: look-ahead depth 3 only with compiler-visible staging reads");
         const long long m0f = rowfn(F);
         const bool has1 = p.res1 != nullptr;
         E4Res n3 = n2;
-        if constexpr (F + D < MF) {
-            if (has1) e4_load_res<NF>(p, rowfn(F + D), nw0, lane, D == 1 ? n1 : (D == 2 ? n2 : n3));
+        if constexpr (F + 1 < MF) {
+            if (has1) e4_load_res<NF>(p, rowfn(F + 1), nw0, lane, n1);
         }
-        if constexpr (F >= D) {
-            // pieces of fragment F: issued at the top of fragment F - D; behind them D fragments' stores and the loads of the fragments
-            // F + 1 .. F + D that exist (the prologue's pieces, F < D, landed in the constants' wait)
-            constexpr int younger_loads = (F + D < MF ? D : (MF - 1 - F > 0 ? MF - 1 - F : 0));
-            if (has1) e4_wait_cnt<D * E4Cnt<NF>::STORES + younger_loads * E4Cnt<NF>::LOADS>(cur);
+        if constexpr (F >= 1) {
+            // pieces of fragment F: issued at the top of fragment F - 1; behind them that fragment's stores and the loads of fragment F + 1
+            // if it exists (the prologue's pieces, F = 0, landed in the constants' wait)
+            if (has1) e4_wait_cnt<E4Cnt<NF>::STORES + (F + 1 < MF ? E4Cnt<NF>::LOADS : 0)>(cur);
         }
         bool regroup = false;
         if constexpr (F > 0) {
@@ -905,37 +845,30 @@ __device__ __forceinline__ void e4_retire(const GP& p, const Acc& acc, long long
         }
         {
             f32x4 accf[NF];
-            acc.template get<F>(accf);
+#pragma unroll
+            for (int j = 0; j < NF; ++j) accf[j] = acc[F][j];
             e4_fragment<NF, GN, RD>(p, accf, m0f, nw0, lane, stage, cur, t, gn);
         }
         if constexpr (GN) {
             unsigned slot = 0, sid = 0;
             if (flushfn(F, m0f, slot, sid)) gn_flush<NF>(p, gn, (long long)sid, nw0, lane, stage, slot);
         }
-        e4_retire<F + 1, MF, NF, GN, D, RD>(p, acc, nw0, lane, stage, n1, n2, n3, t, gn, rowfn, flushfn);
+        e4_retire<F + 1, MF, NF, GN, RD>(p, acc, nw0, lane, stage, n1, n2, n3, t, gn, rowfn, flushfn);
     }
 }
-template <int MF, int NF, bool GN, int D = E4_DEPTH, int RD = E4_ASM_READS, typename Acc, typename RowFn, typename FlushFn>
-__device__ __forceinline__ void e4_retire_tile_src(const GP& p, const Acc& acc, long long nw0, int lane, unsigned char* stage, RowFn rowfn, FlushFn flushfn) {
+template <int MF, int NF, bool GN, int RD = E4_ASM_READS, typename RowFn, typename FlushFn>
+__device__ __forceinline__ void e4_retire_tile(const GP& p, f32x4 (&acc)[MF][NF], long long nw0, int lane, unsigned char* stage, RowFn rowfn, FlushFn flushfn) {
     E4Res r0, r1, r2;
     r0.a0 = r0.a1 = r0.a2 = u32x4{0u, 0u, 0u, 0u};
     r1 = r0;
     r2 = r0;
-    if (p.res1) {
-        e4_load_res<NF>(p, rowfn(0), nw0, lane, r0);
-        if constexpr (D >= 2 && MF > 1) e4_load_res<NF>(p, rowfn(1), nw0, lane, r1);
-        if constexpr (D >= 3 && MF > 2) e4_load_res<NF>(p, rowfn(2), nw0, lane, r2);
-    }
+    if (p.res1) e4_load_res<NF>(p, rowfn(0), nw0, lane, r0);
     E4Tile<NF> t;
     e4_tile_consts<NF>(p, rowfn(0), nw0, lane, t);          // (its vmcnt(0) also lands the residual pieces issued above)
     asm volatile("" : "+v"(r0.a0), "+v"(r0.a1), "+v"(r0.a2), "+v"(r1.a0), "+v"(r1.a1), "+v"(r1.a2), "+v"(r2.a0), "+v"(r2.a1), "+v"(r2.a2));
     GnAcc<GN ? NF : 1> gn;
     if constexpr (GN) gn_zero(gn);
-    e4_retire<0, MF, NF, GN, D, RD>(p, acc, nw0, lane, stage, r0, r1, r2, t, gn, rowfn, flushfn);
-}
-template <int MF, int NF, bool GN, int D = E4_DEPTH, int RD = E4_ASM_READS, typename RowFn, typename FlushFn>
-__device__ __forceinline__ void e4_retire_tile(const GP& p, f32x4 (&acc)[MF][NF], long long nw0, int lane, unsigned char* stage, RowFn rowfn, FlushFn flushfn) {
-    e4_retire_tile_src<MF, NF, GN, D, RD>(p, E4AccArray<MF, NF>{acc}, nw0, lane, stage, rowfn, flushfn);
+    e4_retire<0, MF, NF, GN, RD>(p, acc, nw0, lane, stage, r0, r1, r2, t, gn, rowfn, flushfn);
 }
 
 // ---- stream-K tail ------------------------------------------------------------------------------------------------------------------------

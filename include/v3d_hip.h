@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define V3D_ABI_VERSION 6
+#define V3D_ABI_VERSION 7
 
 typedef void* v3d_stream_t; /* hipStream_t */
 
@@ -245,7 +245,9 @@ int v3d_quant_fp8_slab(const void* vT, void* v8, float* vscale, void* amax_scrat
 int v3d_attn_spatial_fp8(const void* qk8, int64_t ld8, const float* scales, const void* v8, const float* vscale, void* out, int64_t ldo,
                          int64_t n_img, int64_t S, int32_t heads, float scale, v3d_stream_t stream);
 
-/* Temporal self-attention over the frame axis (Tq local queries x Tk keys, Tq,Tk <= 32), head dim 64.
+/* Temporal self-attention over the frame axis (Tq local queries x Tk keys, 1 <= Tq,Tk <= 1024; ABI 7, up to 32 before), head dim 64.
+ * Tq,Tk <= 32: one 32-frame tile per problem (the kernels of ABI <= 6, unchanged); beyond: 32-query tiles streaming 32-key tiles with an
+ * online softmax.  bf16 in / out, fp32 softmax and accumulation, deterministic (no atomics).
  *   problem p = (b, s, h); element (b, t, s, h*64+d) of q at q + b*q_sb + t*q_st + s*q_ss + h*64 + d (same for k, v, out).
  * replaces VideoTransformerBlock.attn1 on "(b t) s c -> (b s) t c" (video_attention.py:114,122-125) without the
  * two full-tensor transposes. */

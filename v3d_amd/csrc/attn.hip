@@ -813,6 +813,167 @@ __global__ __launch_bounds__(256) void attn_temporal_mfma_kernel(TP p) {
     }
 }
 
+// ------------------------------------------------------------------------------------------------------
+// Temporal self-attention for more than 32 frames (Tq > 32 or Tk > 32, both <= TLONG_MAX).  One wave per (problem, 32-query tile):
+// wave w -> problem w / nqt, queries 32 (w % nqt) .. +31, so the query tiles of one problem run in neighbouring waves and their K | V
+// re-reads come from L2.  The operand scheme is that of attn_temporal_mfma_kernel above (S^T = K Q^T, O^T = V^T P^T with the slot order
+// that needs no lane exchange, V in the wave's LDS at the 144-byte pitch); the keys stream in 32-frame tiles with an online softmax:
+//   per query: running max m (log2 units) and running sum l; at each key tile  m' = max(m, tile max),  a = exp2(m - m'),
+//   P = bf16(exp2(s - m')),  l = a l + sum(P),  O = a O + V^T P^T,  and out = O / l after the last tile.
+// P is rounded to bf16 against the running max of its tile and l sums exactly the rounded weights that enter O: the convention of the
+// short kernels, per tile.
+// Invariant: a key tile starts at k0 < Tk (loop condition), so every tile holds at least one valid key, the tile max of finite scores is
+// finite, and so is m after the first tile - a = exp2(-inf - m') = 0 there clears the (zero) O and l, and no -inf - -inf ever occurs.
+// Rows past Tk / Tq are loaded from the last valid frame (clamped, finite): keys past Tk are masked to -inf (P = 0 against a finite V row),
+// queries past Tq are computed and never stored.  The tile's loads are not double-buffered in registers: that needs ~150 VGPRs (2 waves
+// per SIMD, or spills at 4); without it the kernel holds 4 waves per SIMD and the other waves of the SIMD cover the load latency.
+// ------------------------------------------------------------------------------------------------------
+constexpr int TLONG_MAX = 1024;
+
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void attn_temporal_long_kernel(TP p) {
+    constexpr int VP = 72;                                  // LDS row pitch of V in bf16 (144 bytes)
+    __shared__ __attribute__((aligned(16))) bf16_t sVall[4][32 * VP];
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int Tq = p.Tq, Tk = p.Tk;
+    const int nqt = (Tq + 31) >> 5;
+    const long long w = (long long)blockIdx.x * 4 + wave;
+    const long long pp = w / nqt;
+    if (pp >= p.P) return;                                  // (wave-uniform; the LDS region is wave-private: no block barrier below)
+    const int q0 = (int)(w - pp * nqt) * 32;
+    bf16_t* sv = sVall[wave];
+    const int h = (int)(pp % p.heads);
+    const long long bs = pp / p.heads;
+    const long long s = bs % p.S, b = bs / p.S;
+    const int m = lane & 15, g = lane >> 4;
+    const bf16_t* qb = p.q + b * p.q_sb + s * p.q_ss + h * 64;
+    const bf16_t* kb = p.k + b * p.kv_sb + s * p.kv_ss + h * 64;
+    const bf16_t* vb = p.v + b * p.kv_sb + s * p.kv_ss + h * 64;
+
+    u32x4 qf[2][2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+        const int row = min(q0 + 16 * t + m, Tq - 1);
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) qf[t][ks] = *reinterpret_cast<const u32x4*>(qb + (long long)row * p.q_st + ks * 32 + g * 8);
+    }
+    // key tile at k0: V chunk c = u * 64 + lane (frame k0 + (c >> 3), channels 8 (c & 7) ..), K operand rows k0 + 16 t + m
+    struct KVTile { u32x4 v[4], k[2][2]; };
+    auto load_tile = [&](int k0) __attribute__((always_inline)) {
+        KVTile r;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int c = u * 64 + lane;
+            r.v[u] = *reinterpret_cast<const u32x4*>(vb + (long long)min(k0 + (c >> 3), Tk - 1) * p.kv_st + (c & 7) * 8);
+        }
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            const int row = min(k0 + 16 * t + m, Tk - 1);
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks) r.k[t][ks] = *reinterpret_cast<const u32x4*>(kb + (long long)row * p.kv_st + ks * 32 + g * 8);
+        }
+        return r;
+    };
+
+    const float sl2 = p.scale * 1.44269504088896340736f;
+    float m_run[2] = {-INFINITY, -INFINITY}, l_run[2] = {0.f, 0.f};
+    f32x4 oacc[2][4];
+#pragma unroll
+    for (int it = 0; it < 2; ++it)
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) oacc[it][dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const unsigned short* svu = reinterpret_cast<const unsigned short*>(sv);
+
+    for (int k0 = 0; k0 < Tk; k0 += 32) {
+        const KVTile cur = load_tile(k0);
+
+        // ---- S^T = K Q^T for this key tile
+        f32x4 sacc[2][2];
+#pragma unroll
+        for (int jt = 0; jt < 2; ++jt)
+#pragma unroll
+            for (int it = 0; it < 2; ++it) {
+                sacc[jt][it] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int ks = 0; ks < 2; ++ks)
+                    sacc[jt][it] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, cur.k[jt][ks]), __builtin_bit_cast(bf16x8, qf[it][ks]),
+                                                                           sacc[jt][it], 0, 0, 0);
+            }
+
+        // ---- online softmax: lane (query m of tile it, g) holds keys k0 + 16 (e >> 2) + 4 g + (e & 3); the rest of the row in lanes +-16, +-32
+        uint4 pf[2];
+#pragma unroll
+        for (int it = 0; it < 2; ++it) {
+            float v[8];
+            float mx = -INFINITY;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const int key = k0 + 16 * (e >> 2) + 4 * g + (e & 3);
+                v[e] = key < Tk ? sacc[e >> 2][it][e & 3] * sl2 : -INFINITY;
+                mx = fmaxf(mx, v[e]);
+            }
+            mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+            mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+            const float mn = fmaxf(m_run[it], mx);
+            const float a = __builtin_amdgcn_exp2f(m_run[it] - mn);
+            m_run[it] = mn;
+            uint32_t wpk[4];
+            float l = 0.f;
+#pragma unroll
+            for (int e = 0; e < 8; e += 2) {
+                wpk[e >> 1] = pack2bf(__builtin_amdgcn_exp2f(v[e] - mn), __builtin_amdgcn_exp2f(v[e + 1] - mn));
+                l += bflo(wpk[e >> 1]) + bfhi(wpk[e >> 1]);
+            }
+            l += __shfl_xor(l, 16, 64);
+            l += __shfl_xor(l, 32, 64);
+            l_run[it] = l_run[it] * a + l;
+#pragma unroll
+            for (int dt = 0; dt < 4; ++dt) oacc[it][dt] *= a;
+            pf[it] = make_uint4(wpk[0], wpk[1], wpk[2], wpk[3]);
+        }
+
+        // ---- this tile's V rows into the wave's LDS: every lane has finished reading the previous tile's rows first
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int c = u * 64 + lane;
+            *reinterpret_cast<u32x4*>(sv + (c >> 3) * VP + (c & 7) * 8) = cur.v[u];
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+
+        // ---- O^T += V^T P^T
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) {
+            uint32_t a4[4];
+#pragma unroll
+            for (int e = 0; e < 8; e += 2) {
+                const int k = 16 * (e >> 2) + 4 * g + (e & 3);
+                a4[e >> 1] = (uint32_t)svu[k * VP + 16 * dt + m] | ((uint32_t)svu[(k + 1) * VP + 16 * dt + m] << 16);
+            }
+            const bf16x8 vf = __builtin_bit_cast(bf16x8, make_uint4(a4[0], a4[1], a4[2], a4[3]));
+#pragma unroll
+            for (int it = 0; it < 2; ++it) oacc[it][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, __builtin_bit_cast(bf16x8, pf[it]), oacc[it][dt], 0, 0, 0);
+        }
+    }
+
+    // ---- out[query q0 + 16 it + m][channels 16 dt + 4 g ..]: 8 bytes per (it, dt)
+#pragma unroll
+    for (int it = 0; it < 2; ++it) {
+        const int i = q0 + 16 * it + m;
+        if (i < Tq) {
+            const float inv = 1.0f / l_run[it];
+            bf16_t* op = p.out + b * p.o_sb + (long long)i * p.o_st + s * p.o_ss + h * 64 + 4 * g;
+#pragma unroll
+            for (int dt = 0; dt < 4; ++dt)
+                *reinterpret_cast<uint2*>(op + 16 * dt) = make_uint2(pack2bf(oacc[it][dt][0] * inv, oacc[it][dt][1] * inv),
+                                                                     pack2bf(oacc[it][dt][2] * inv, oacc[it][dt][3] * inv));
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" int v3d_attn_spatial(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* vT, void* out,
@@ -852,7 +1013,7 @@ extern "C" int v3d_attn_temporal(const void* q, int64_t q_sb, int64_t q_st, int6
                                  int64_t B, int32_t Tq, int32_t Tk, int64_t S, int32_t heads, float scale,
                                  v3d_stream_t stream) {
     V3D_REQUIRE(q && k && v && out, "v3d_attn_temporal: null pointer");
-    V3D_REQUIRE(Tq >= 1 && Tq <= TMAX && Tk >= 1 && Tk <= TMAX, "v3d_attn_temporal: Tq/Tk must be in [1,%d] (got %d,%d)", TMAX, Tq, Tk);
+    V3D_REQUIRE(Tq >= 1 && Tq <= TLONG_MAX && Tk >= 1 && Tk <= TLONG_MAX, "v3d_attn_temporal: Tq/Tk must be in [1,%d] (got %d,%d)", TLONG_MAX, Tq, Tk);
     V3D_REQUIRE(B > 0 && S > 0 && heads > 0, "v3d_attn_temporal: bad sizes");
     V3D_REQUIRE((q_sb | q_st | q_ss | kv_sb | kv_st | kv_ss | o_sb | o_st | o_ss) % 8 == 0, "v3d_attn_temporal: strides must be multiples of 8 elements");
     V3D_REQUIRE((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)out) & 15) == 0, "v3d_attn_temporal: misaligned pointer");
@@ -861,9 +1022,17 @@ extern "C" int v3d_attn_temporal(const void* q, int64_t q_sb, int64_t q_st, int6
     p.k = (const bf16_t*)k; p.v = (const bf16_t*)v; p.kv_sb = kv_sb; p.kv_st = kv_st; p.kv_ss = kv_ss;
     p.out = (bf16_t*)out; p.o_sb = o_sb; p.o_st = o_st; p.o_ss = o_ss;
     p.P = (long long)B * S * heads; p.S = S; p.heads = heads; p.Tq = Tq; p.Tk = Tk; p.scale = scale;
+    if (Tq > TMAX || Tk > TMAX) {
+        p.G = 1;
+        const long long waves = p.P * ((Tq + 31) / 32);     // one wave per (problem, 32-query tile)
+        const long long blocks = (waves + 3) / 4;
+        V3D_REQUIRE(blocks < (1ll << 31), "v3d_attn_temporal: grid too large");
+        hipLaunchKernelGGL(attn_temporal_long_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p);
+        return v3d_check_launch("v3d_attn_temporal");
+    }
     static int timpl = -1;
     if (timpl < 0) {
-        const char* e = getenv("V3D_ATTN_TEMPORAL_IMPL");   // A/B knob: 1 = the VALU (dot2) kernel of rounds 1-4, 2 = the MFMA kernel (default)
+        const char* e = getenv("V3D_ATTN_TEMPORAL_IMPL");   // A/B knob (Tq, Tk <= 32): 1 = the VALU (dot2) kernel of rounds 1-4, 2 = the MFMA kernel (default)
         timpl = e ? atoi(e) : 2;
     }
     if (timpl != 1) {

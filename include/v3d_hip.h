@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define V3D_ABI_VERSION 7
+#define V3D_ABI_VERSION 8
 
 typedef void* v3d_stream_t; /* hipStream_t */
 
@@ -229,6 +229,14 @@ int v3d_layernorm(const void* x, const float* add, int64_t add_rpg, int64_t add_
  * ---------------------------------------------------------------------------------------------- */
 int v3d_attn_spatial(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* vT, void* out,
                      int64_t ldo, int64_t n_img, int64_t S, int32_t heads, float scale, v3d_stream_t stream);
+
+/* The same attention for any token count S >= 1 (ABI 8; v3d_attn_spatial needs S % 8 == 0): V^T rows carry their own stride,
+ *   vT[n][h*64+d][s] at vT + (n*heads*64 + h*64 + d)*ldv + s,   ldv >= S and a multiple of 8 (16-byte row starts).
+ * Pad contract: the columns S..ldv-1 of every V^T row may hold anything (NaN included); they never reach the output.  ldv == S with
+ * S % 8 == 0 runs exactly v3d_attn_spatial.  Everything else follows v3d_attn_spatial.  Used by the U-Net levels whose token count
+ * (H/64)(W/64) or 4(H/64)(W/64) is not a multiple of 8 (e.g. 81 and 324 at 576 x 576). */
+int v3d_attn_spatial_ld(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* vT, int64_t ldv, void* out,
+                        int64_t ldo, int64_t n_img, int64_t S, int32_t heads, float scale, v3d_stream_t stream);
 
 /* fp8 (OCP e4m3fn) variant of the spatial self-attention (ABI 3) - BASELINE.json configs[4] ("scene" shape, 9216 tokens at level 0) names
  * fp8 MFMA attention; the reference has no fp8 path, parity is stated against v3d_attn_spatial (tests: cosine >= 0.995).  Never used by the

@@ -15,6 +15,7 @@ from __future__ import annotations
 
 import argparse
 import math
+import numbers
 import os
 import sys
 from typing import Any, Optional
@@ -93,6 +94,14 @@ def load_clip_model(device: str, ckpt_path: Optional[str] = None, synthetic: boo
     return clip_model.to(device)
 
 
+def check_size(height: int, width: int):
+    """The U-Net halves the 1/8-scale latent three times and concatenates skips of equal size: both sides must be positive multiples of 64 px
+    (the reference fails on other sizes with a shape error deep inside the U-Net)."""
+    for name, v in (("height", height), ("width", width)):
+        if isinstance(v, bool) or not isinstance(v, numbers.Integral) or v <= 0 or v % 64:
+            raise ValueError(f"{name} must be a positive multiple of 64 pixels (got {v!r}): the U-Net downsamples the 1/8 latent three times")
+
+
 @torch.no_grad()
 def sample_one(input_path: str = "assets/test_image.png", checkpoint_path: Optional[str] = None, num_frames: Optional[int] = None,
                num_steps: Optional[int] = None, fps_id: int = 1, motion_bucket_id: int = 300, cond_aug: float = 0.02, seed: int = 23,
@@ -104,6 +113,7 @@ def sample_one(input_path: str = "assets/test_image.png", checkpoint_path: Optio
                height: int = 512, width: int = 512, model_channels: int = 320, vae_ch: int = 128,
                ae_checkpoint_path: Optional[str] = None, sampler: str = "euler"):
     """Returns (frames uint8 [T, H, W, 3] on the host, model).  Keyword arguments up to `ignore_alpha` are the reference's."""
+    check_size(height, width)
     num_frames = 18 if num_frames is None else num_frames       # the reference reads it from the guider config (18)
     num_steps = 25 if num_steps is None else num_steps
     decoding_t = min(decoding_t, num_frames)
@@ -231,9 +241,15 @@ def main():
     ap.add_argument("--border_ratio", type=float, default=0.3, help="reference argument of its rembg / kiui recentering step, which this build does "
                                                                     "not run: the input must already be a prepared (matted, centred) RGB view")
     ap.add_argument("--ignore_alpha", action="store_true")
+    ap.add_argument("--height", type=int, default=512, help="output height in pixels, a multiple of 64")
+    ap.add_argument("--width", type=int, default=512, help="output width in pixels, a multiple of 64")
     ap.add_argument("--sampler", default="euler", choices=list(configs.SAMPLERS),
                     help="sampler of the built-in config (default: the reference's EulerEDMSampler); ignored with --config")
     a = ap.parse_args()
+    try:
+        check_size(a.height, a.width)
+    except ValueError as e:
+        ap.error(str(e))
     if not os.path.isfile(a.input_path) and not a.synthetic:
         raise SystemExit(f"input image {a.input_path} not found (pass --synthetic to run on synthetic conditioning)")
     image = None
@@ -242,16 +258,16 @@ def main():
         if _Image.open(a.input_path).mode in ("RGBA", "LA") and not a.ignore_alpha:
             print("warning: the input has an alpha channel; the reference composites it on white after rembg / recentering (border_ratio "
                   f"{a.border_ratio}) - this build takes the RGB channels as they are")
-        # plain load + resize to 512 x 512 -> [-1, 1]; the reference's matting / recentering (rembg, kiui) stays outside this build
+        # plain load + resize to width x height -> [-1, 1]; the reference's matting / recentering (rembg, kiui) stays outside this build
         from PIL import Image
         import numpy as np
-        im = Image.open(a.input_path).convert("RGB").resize((512, 512))
+        im = Image.open(a.input_path).convert("RGB").resize((a.width, a.height))
         image = torch.from_numpy(np.asarray(im).copy()).permute(2, 0, 1)[None].float() / 127.5 - 1.0
     frames, _ = sample_one(a.input_path, a.checkpoint_path, a.num_frames, a.num_steps, a.fps_id, a.motion_bucket_id, a.cond_aug, a.seed,
                            a.decoding_t, a.device, a.output_folder, save=a.save, min_guidance_scale=a.min_guidance_scale,
                            max_guidance_scale=a.max_guidance_scale, sigma_max=a.sigma_max, config=a.config, synthetic=a.synthetic, image=image,
                            clip_checkpoint_path=a.clip_checkpoint_path, ae_checkpoint_path=a.ae_checkpoint_path, border_ratio=a.border_ratio,
-                           ignore_alpha=a.ignore_alpha, sampler=a.sampler)
+                           ignore_alpha=a.ignore_alpha, sampler=a.sampler, height=a.height, width=a.width)
     print("frames", frames.shape, frames.dtype, "mean", float(frames.mean()))
     # parity status of what just ran: sampler / U-Net / decoder / VAE encoder are pinned to fixtures generated from the
     # reference's own modules; the OpenCLIP ViT tower is pinned to transformers' implementation of the same architecture (tests/golden/clip_tower.pt);

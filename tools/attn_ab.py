@@ -1,5 +1,7 @@
 """Interleaved same-process A/B of several builds of libv3d_hip.so on the spatial self-attention launches of the V3D_512 evaluation
-(tools/mainloop_ab.py for the attention kernels): python tools/attn_ab.py base=path new=path ... -> median us, TF/s, max |diff| vs the first."""
+(tools/mainloop_ab.py for the attention kernels): python tools/attn_ab.py base=path new=path ... -> median us, TF/s, max |diff| vs the first.
+--ragged adds token counts that are not multiples of 8 (the deepest levels of a 576 x 576 and a 1216 x 1216 image, V^T rows padded to a multiple
+of 8: v3d_attn_spatial_ld) beside the dense counts of the levels they replace."""
 import os
 import statistics
 import sys
@@ -14,12 +16,15 @@ libs = [a.split("=", 1) for a in sys.argv[1:] if "=" in a and not a.startswith("
 hips = [(t, HipOps(lib_path=os.path.join(ROOT, p) if not os.path.isabs(p) else p)) for t, p in libs]
 BF = torch.bfloat16
 print(f"{'case':22s}" + "".join(f"{t:>10s}" for t, _ in hips))
-for n, S, h in ((36, 4096, 5), (36, 1024, 10), (36, 256, 20)):
+CASES = ((36, 4096, 5), (36, 1024, 10), (36, 256, 20))
+if "--ragged" in sys.argv:
+    CASES += ((36, 64, 20), (36, 81, 20), (36, 256, 20), (36, 324, 20), (36, 1024, 10), (36, 1444, 10))
+for n, S, h in CASES:
     C = h * 64
     g = torch.Generator(device="cuda").manual_seed(1)
     q = torch.randn(n * S, C, device="cuda", generator=g).to(BF)
     k = torch.randn(n * S, C, device="cuda", generator=g).to(BF)
-    vT = torch.randn(n, C, S, device="cuda", generator=g).to(BF)
+    vT = torch.randn(n, C, -(-S // 8) * 8, device="cuda", generator=g).to(BF)[..., :S]
     outs = [torch.zeros(n * S, C, dtype=BF, device="cuda") for _ in hips]
     for (t, hp), o in zip(hips, outs):
         hp.attn_spatial(q, k, vT, o, n, S, h, 0.125)

@@ -196,11 +196,17 @@ __global__ __launch_bounds__(256, 2) void attn_spatial_kernel(const bf16_t* __re
 #define ATTN_PIPE 1
 #endif
 
-template <int QG>
+// RAG (ragged token count, v3d_attn_spatial_ld): any S >= 1, V^T rows at their own stride ldv (a multiple of 8, >= S; ignored when RAG is
+// false, where the stride is S).  Keys >= S are masked twice in the last tile: their scores are -inf (as for any S) and their V^T lanes are
+// zeroed in the tile's LDS stage (read-modify-write of the chunks that hold them, then one extra barrier), because the pad columns S..ldv-1 and the
+// next d-row that the tail chunks reach may hold anything and 0 * NaN is NaN.  (Masking the fragments in registers instead forced the last tile
+// off the pipelined softmax path; the QG = 2 instantiation then spilled 208 bytes.)
+// The RAG = false instantiations compile to the kernels of ABI <= 7.
+template <int QG, bool RAG>
 __global__ __launch_bounds__(256, 2) void attn_spatial_v2_kernel(const bf16_t* __restrict__ q, long long ldq,
                                                                  const bf16_t* __restrict__ k, long long ldk,
                                                                  const bf16_t* __restrict__ vT, bf16_t* __restrict__ out,
-                                                                 long long ldo, long long S, int heads, float scale2) {
+                                                                 long long ldo, long long S, int heads, float scale2, long long ldv) {
     constexpr int NS = 3;
     constexpr int TILE_BYTES = 2 * 64 * 128;   // K tile (64 keys x 128 B) + V^T tile (64 d-rows x 128 B)
     constexpr int PIECES = 4;                  // per wave per tile: 2 K pieces + 2 V pieces (8 rows x 128 B each)
@@ -242,14 +248,15 @@ __global__ __launch_bounds__(256, 2) void attn_spatial_v2_kernel(const bf16_t* _
     //      recomputed 64-bit pointers with bounds selects per tile: ~60 VALU / SALU instructions, 15 % of the loop.)
     const int prow = lane >> 3;
     const bufrsrc_t rsK = make_rsrc(k + n * S * ldk + h * 64, (unsigned)(((S - 1) * ldk + 64) * 2));
-    const bufrsrc_t rsV = make_rsrc(vT + (n * C + h * 64) * S, (unsigned)(64 * S * 2));
+    const long long vld = RAG ? ldv : S;                     // V^T row stride
+    const bufrsrc_t rsV = make_rsrc(vT + (n * C + h * 64) * vld, (unsigned)(64 * vld * 2));
     unsigned koffs[2], voffs[2];
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
         const int row = (wave * 2 + i) * 8 + prow;          // key row within the tile / d row of V^T
         const int ch = (lane & 7) ^ ((row >> 1) & 7);
         koffs[i] = (unsigned)((row * ldk + ch * 8) * 2);
-        voffs[i] = (unsigned)(((long long)row * S + ch * 8) * 2);
+        voffs[i] = (unsigned)(((long long)row * vld + ch * 8) * 2);
     }
     const unsigned kstep = (unsigned)(64 * ldk * 2);
     const int ntiles = (int)((S + 63) / 64);
@@ -305,6 +312,26 @@ __global__ __launch_bounds__(256, 2) void attn_spatial_v2_kernel(const bf16_t* _
         const unsigned char* sb = lds + (t % NS) * TILE_BYTES;
         const long long k0 = (long long)t * 64;
         const bool tail = (k0 + 64 > S);
+        if constexpr (RAG) {
+            if (tail) {   // zero the V^T lanes of keys >= S in this stage: 64 d-rows x 8 chunks, two per thread; every wave reads every row -> one barrier
+                unsigned char* sv = lds + (t % NS) * TILE_BYTES + 8192;
+#pragma unroll
+                for (int i = 0; i < 2; ++i) {
+                    const int c = tid + 256 * i, row = c >> 3, lch = c & 7;          // logical chunk lch = keys k0 + 8 lch + (0..7)
+                    const int nv = (int)(S - k0) - 8 * lch;
+                    if (nv < 8) {
+                        u32x4* cp = reinterpret_cast<u32x4*>(sv + row * 128 + ((lch ^ ((row >> 1) & 7)) * 16));
+                        u32x4 u = *cp;
+#pragma unroll
+                        for (int w = 0; w < 4; ++w) u[w] &= (2 * w < nv ? 0x0000FFFFu : 0u) | (2 * w + 1 < nv ? 0xFFFF0000u : 0u);
+                        *cp = u;
+                    }
+                }
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                __builtin_amdgcn_s_barrier();
+                asm volatile("" ::: "memory");
+            }
+        }
 
         // ---- S^T = K . Q^T for both 32-key halves ----
         f32x16 sT[QG][2];
@@ -997,14 +1024,38 @@ extern "C" int v3d_attn_spatial(const void* q, int64_t ldq, const void* k, int64
                            (const bf16_t*)k, (long long)ldk, (const bf16_t*)vT, (bf16_t*)out, (long long)ldo, (long long)S, heads, sc2);
     } else if (S >= 1024 && impl != 3) {
         dim3 grid((unsigned)((S + 255) / 256), (unsigned)heads, (unsigned)n_img);
-        hipLaunchKernelGGL(attn_spatial_v2_kernel<2>, grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)q, (long long)ldq,
-                           (const bf16_t*)k, (long long)ldk, (const bf16_t*)vT, (bf16_t*)out, (long long)ldo, (long long)S, heads, sc2);
+        hipLaunchKernelGGL((attn_spatial_v2_kernel<2, false>), grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)q, (long long)ldq,
+                           (const bf16_t*)k, (long long)ldk, (const bf16_t*)vT, (bf16_t*)out, (long long)ldo, (long long)S, heads, sc2, (long long)S);
     } else {
         dim3 grid((unsigned)((S + 127) / 128), (unsigned)heads, (unsigned)n_img);
-        hipLaunchKernelGGL(attn_spatial_v2_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)q, (long long)ldq,
-                           (const bf16_t*)k, (long long)ldk, (const bf16_t*)vT, (bf16_t*)out, (long long)ldo, (long long)S, heads, sc2);
+        hipLaunchKernelGGL((attn_spatial_v2_kernel<1, false>), grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)q, (long long)ldq,
+                           (const bf16_t*)k, (long long)ldk, (const bf16_t*)vT, (bf16_t*)out, (long long)ldo, (long long)S, heads, sc2, (long long)S);
     }
     return v3d_check_launch("v3d_attn_spatial");
+}
+
+extern "C" int v3d_attn_spatial_ld(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* vT, int64_t ldv, void* out,
+                                   int64_t ldo, int64_t n_img, int64_t S, int32_t heads, float scale, v3d_stream_t stream) {
+    if (ldv == S && S % 8 == 0)         // dense V^T: the kernels and launch configuration of v3d_attn_spatial
+        return v3d_attn_spatial(q, ldq, k, ldk, vT, out, ldo, n_img, S, heads, scale, stream);
+    V3D_REQUIRE(q && k && vT && out, "v3d_attn_spatial_ld: null pointer");
+    V3D_REQUIRE(n_img > 0 && n_img <= 65535 && heads > 0 && heads <= 65535 && S > 0, "v3d_attn_spatial_ld: bad sizes");
+    V3D_REQUIRE(ldv >= S && ldv % 8 == 0, "v3d_attn_spatial_ld: ldv must be >= S and a multiple of 8 (S=%lld ldv=%lld)", (long long)S, (long long)ldv);
+    V3D_REQUIRE(ldq % 8 == 0 && ldk % 8 == 0 && ldo % 4 == 0, "v3d_attn_spatial_ld: ldq/ldk must be multiples of 8, ldo of 4");
+    V3D_REQUIRE((((uintptr_t)q | (uintptr_t)k | (uintptr_t)vT) & 15) == 0 && ((uintptr_t)out & 7) == 0, "v3d_attn_spatial_ld: misaligned pointer");
+    V3D_REQUIRE((unsigned long long)(S + 192) * (ldq > ldk ? ldq : ldk) * 2ull <= kMaxBufBytes && (unsigned long long)(64 * ldv + 256) * 2ull <= kMaxBufBytes,
+                "v3d_attn_spatial_ld: per-image q / k / v slab exceeds 4 GiB");
+    const float sc2 = scale * 1.44269504088896340736f;
+    if (S >= 1024) {
+        dim3 grid((unsigned)((S + 255) / 256), (unsigned)heads, (unsigned)n_img);
+        hipLaunchKernelGGL((attn_spatial_v2_kernel<2, true>), grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)q, (long long)ldq,
+                           (const bf16_t*)k, (long long)ldk, (const bf16_t*)vT, (bf16_t*)out, (long long)ldo, (long long)S, heads, sc2, (long long)ldv);
+    } else {
+        dim3 grid((unsigned)((S + 127) / 128), (unsigned)heads, (unsigned)n_img);
+        hipLaunchKernelGGL((attn_spatial_v2_kernel<1, true>), grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)q, (long long)ldq,
+                           (const bf16_t*)k, (long long)ldk, (const bf16_t*)vT, (bf16_t*)out, (long long)ldo, (long long)S, heads, sc2, (long long)ldv);
+    }
+    return v3d_check_launch("v3d_attn_spatial_ld");
 }
 
 extern "C" int v3d_attn_temporal(const void* q, int64_t q_sb, int64_t q_st, int64_t q_ss,

@@ -173,7 +173,7 @@ def cross_attention_module(at, x, context=None, mask=None):
     assert at.dim_head == 64, "attention kernels are specialised for dim_head = 64"
     rows = _tokens(ops, x)
     q, k = ops.linear(rows, wq), ops.linear(rows, wk)
-    vT = ops.empty((B, inner, N), ops.act_dtype, dev)
+    vT = ops.empty((B, inner, N), ops.act_dtype, dev) if N % 8 == 0 else ops.empty((B, inner, -(-N // 8) * 8), ops.act_dtype, dev)[..., :N]  # padded rows
     ops.gemm(GemmCall(A=wv, W=rows.view(B, N, C), out=vT, M=inner, N=N, K=C, batch=B))
     a = ops.empty((B * N, inner), ops.act_dtype, dev)
     ops.attn_spatial(q, k, vT, a, B, N, at.heads, float(at.scale))

@@ -93,8 +93,9 @@ def run_svt(env: Env, g: Geo, p: SVTPack, x_in: torch.Tensor) -> torch.Tensor:
         n1 = ops.empty((n * S, C), ops.act_dtype, x.device)
         ops.layernorm(x, ga, be, n1, eps)
         qk = ops.linear(n1, p.s_wqk)
-        # V^T[img] = Wv @ LN(x)[img]^T directly out of the projection: keys contiguous for the P.V MFMA, no transpose
-        vT = ops.empty((n, C, S), ops.act_dtype, x.device)
+        # V^T[img] = Wv @ LN(x)[img]^T directly out of the projection: keys contiguous for the P.V MFMA, no transpose.  A token count that is
+        # not a multiple of 8 gets rows padded to the next multiple (16-byte row starts for the kernel); the projection writes the S valid columns
+        vT = ops.empty((n, C, S), ops.act_dtype, x.device) if S % 8 == 0 else ops.empty((n, C, -(-S // 8) * 8), ops.act_dtype, x.device)[..., :S]
         ops.gemm(GemmCall(A=p.s_wv, W=n1.view(n, S, C), out=vT, M=C, N=S, K=C, batch=n))
     a = ops.empty((n * S, C), ops.act_dtype, x.device)
     if os.environ.get("V3D_ATTN_FP8", "0") not in ("", "0") and hasattr(ops, "attn_spatial_fp8") and S % 16 == 0:

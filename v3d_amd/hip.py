@@ -16,7 +16,7 @@ from .ops import GemmCall, OpsBase
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("V3D_HIP_LIB") or os.path.join(_HERE, "lib", "libv3d_hip.so")     # (override: A/B runs of two builds on one box)
 
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 c_i64, c_i32, c_f32, c_f64, c_vp = C.c_int64, C.c_int32, C.c_float, C.c_double, C.c_void_p
 
@@ -65,6 +65,7 @@ SIGNATURES = {
     "v3d_groupnorm_small": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_i64, c_f32, c_i32, c_vp]),
     "v3d_layernorm": (c_i32, [c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_f32, c_vp]),
     "v3d_attn_spatial": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_i64, c_i32, c_f32, c_vp]),
+    "v3d_attn_spatial_ld": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i64, c_i64, c_i32, c_f32, c_vp]),
     "v3d_attn_temporal": (c_i32, [c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64,
                                   c_i64, c_i64, c_i32, c_i32, c_i64, c_i32, c_f32, c_vp]),
     "v3d_attn_vae_d512": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i32, c_f32, c_vp]),
@@ -380,12 +381,26 @@ class HipOps(OpsBase):
         self._check(self.lib.v3d_layernorm(x.data_ptr(), _ptr(add), add_rpg, add_ld, _ptr(xsum_out), gamma.data_ptr(),
                                            beta.data_ptr(), out.data_ptr(), M, Cc, float(eps), self._stream()), "v3d_layernorm")
 
-    def attn_spatial(self, q, k, vT, out, n_img, S, heads, scale):
+    def attn_spatial(self, q, k, vT, out, n_img, S, heads, scale, ldv=None):
+        """vT: [n_img, C, S], dense or a [..., :S] view of a [n_img, C, ldv] buffer (ldv a multiple of 8; the pad may hold anything).
+        ldv defaults to the row stride of vT.  A dense V^T with S % 8 == 0 runs v3d_attn_spatial, everything else v3d_attn_spatial_ld."""
         bf = torch.bfloat16
-        self._req(q, bf, "attn.q"); self._req(k, bf, "attn.k"); self._req_c(vT, bf, "attn.vT"); self._req(out, bf, "attn.out")
-        self._check(self.lib.v3d_attn_spatial(q.data_ptr(), q.stride(-2), k.data_ptr(), k.stride(-2), vT.data_ptr(),
-                                              out.data_ptr(), out.stride(-2), n_img, S, heads, float(scale), self._stream()),
-                    "v3d_attn_spatial")
+        self._req(q, bf, "attn.q"); self._req(k, bf, "attn.k"); self._req(out, bf, "attn.out")
+        self._req(vT, bf, "attn.vT")
+        if ldv is None:
+            ldv = vT.stride(-2) if vT.dim() >= 2 else S
+        C = heads * 64
+        if vT.dim() == 3 and (vT.shape[-1] != S or vT.stride(0) != C * ldv or vT.stride(1) != ldv):
+            raise RuntimeError(f"attn.vT: expected [n_img, {C}, {S}] rows at stride {ldv}, got shape {tuple(vT.shape)} strides {vT.stride()}")
+        if ldv == S and S % 8 == 0:
+            self._req_c(vT, bf, "attn.vT")
+            self._check(self.lib.v3d_attn_spatial(q.data_ptr(), q.stride(-2), k.data_ptr(), k.stride(-2), vT.data_ptr(),
+                                                  out.data_ptr(), out.stride(-2), n_img, S, heads, float(scale), self._stream()),
+                        "v3d_attn_spatial")
+            return
+        self._check(self.lib.v3d_attn_spatial_ld(q.data_ptr(), q.stride(-2), k.data_ptr(), k.stride(-2), vT.data_ptr(), ldv,
+                                                 out.data_ptr(), out.stride(-2), n_img, S, heads, float(scale), self._stream()),
+                    "v3d_attn_spatial_ld")
 
     def attn_temporal(self, q, k, v, out, heads, scale):
         """q/out: [B, Tq, S, C] views, k/v: [B, Tk, S, C] views (any strides with unit inner stride)."""

@@ -87,8 +87,8 @@ def test_pad_independence(hip_ops, S, ldv):
 
 
 def _fp64_kernel_operands(qk, v, n_img, S, heads):
-    """fp64 attention of the operands the kernel multiplies: q pre-scaled by scale * log2(e) and re-rounded to bf16 once (attn.hip,
-    ATTN_FUSE_MAX: 2^-9 relative per element), the softmax taken in the exp2 domain."""
+    """fp64 attention of the operands the kernel multiplies: q pre-scaled by scale * log2(e) and re-rounded to bf16 once (attn.hip
+    attn_spatial_v2_kernel: 2^-9 relative per element), the softmax taken in the exp2 domain."""
     C = heads * 64
     sc2 = torch.tensor(0.125, dtype=torch.float32) * torch.tensor(1.4426950408889634, dtype=torch.float32)
     q = (qk[:, :C].float() * sc2).to(BF).double().reshape(n_img, S, heads, 64).permute(0, 2, 1, 3)

@@ -1,6 +1,5 @@
 """Temporal attention at the V3D_512 shapes: time per launch and effective HBM rate (q, k, v read + out written once).
-python tools/attn_temporal_bench.py [T ...]: frame counts (default 18; T > 32 runs the long kernel).
-V3D_ATTN_TEMPORAL_IMPL=1 (VALU dot2 kernel of rounds 1-4) / 2 (MFMA kernel, default) is read once per process (T <= 32): run twice for the A/B."""
+python tools/attn_temporal_bench.py [T ...]: frame counts (default 18; T > 32 runs the long kernel)."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -9,7 +8,6 @@ from v3d_amd.ops import get_ops
 torch.set_grad_enabled(False)
 ops = get_ops()
 dev = "cuda"
-print("impl", os.environ.get("V3D_ATTN_TEMPORAL_IMPL", "2 (default)"))
 frames = [int(a) for a in sys.argv[1:]] or [18]
 for (B, T, S, C) in [(b, t, s, c) for t in frames for (b, s, c) in [(2, 4096, 320), (2, 1024, 640), (2, 256, 1280), (2, 64, 1280), (8, 4096, 320)]]:
     heads = C // 64

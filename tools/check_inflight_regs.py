@@ -10,7 +10,7 @@ Known false positive (product build): multi-tap GroupNorm-statistics kernels of 
 `no residual operand` branch around a counted wait AFTER having issued residual loads (the test is launch-invariant; the scanner only recognises
 the simple forms of that correlation).  What a real finding looks like: v_mov_b64 copies whose SOURCE is pending.
 usage: python tools/check_inflight_regs.py v3d_amd/csrc/gemm.hip [kernel-name-substring ...]      (--strict as first argument: exit code 1 on a finding)
-       EXTRA_FLAGS="-DCONV_3X3_READS=2" python tools/check_inflight_regs.py v3d_amd/csrc/conv.hip          audit an A/B build"""
+       EXTRA_FLAGS="-DE4_ASM_READS=2" python tools/check_inflight_regs.py v3d_amd/csrc/gemm.hip            audit an A/B build"""
 import os
 import re
 import subprocess

@@ -28,4 +28,4 @@ for nb in (256, 512, 1024, 1088, 1152, 1216, 1280):
         for _ in range(5): fn()
         e1.record(); torch.cuda.synchronize()
         ts.append(e0.elapsed_time(e1) / 5 * 1e3)
-    print(f"V3D_FF_SPLIT={os.environ.get('V3D_FF_SPLIT','1')} row blocks {nb:5d} ({nb/256:.2f} rounds): {sorted(ts)[2]:7.1f} us", flush=True)
+    print(f"row blocks {nb:5d} ({nb/256:.2f} rounds): {sorted(ts)[2]:7.1f} us", flush=True)

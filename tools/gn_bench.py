@@ -1,4 +1,4 @@
-"""Time the three GroupNorm steps (v3d_groupnorm_stats / finalize / apply) on the V3D shapes (env V3D_GN_BLOCKS = block-count target of the stats grid)."""
+"""Time the three GroupNorm steps (v3d_groupnorm_stats / finalize / apply) on the V3D shapes."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)

@@ -1,6 +1,4 @@
-// Attention kernels for gfx950: spatial (streamed-softmax MFMA, d_head 64) and temporal (T <= 32 frames).
-#include <stdlib.h>
-
+// Attention kernels for gfx950: spatial (streamed-softmax MFMA, d_head 64) and temporal (frame axis, up to 1024 frames).
 #include <type_traits>
 
 #include "common.h"
@@ -8,163 +6,12 @@
 namespace {
 
 // ------------------------------------------------------------------------------------------------------
-// Spatial self-attention.  Block = 4 waves = 128 queries of one (image, head); each wave owns 32 queries.
-// Per 32-key sub-tile a wave computes S^T = K . Q^T with v_mfma_f32_32x32x16_bf16 (A = K rows from LDS,
-// B = Q held in registers), so each lane owns one query column and 16 of its 32 scores: the row max / sum need
-// one cross-lane exchange (lane <-> lane+32) and P^T is already in B-operand position for O^T += V^T . P^T.
-// The contraction index of that second MFMA is a permutation of the keys that is applied identically to the
-// A operand (V^T read from LDS as two 8-byte pieces), so no transpose or lane shuffle of P is needed.
-// V arrives pre-transposed ([C][S], produced directly by the value projection GEMM).
-// ------------------------------------------------------------------------------------------------------
-constexpr int AKT = 64;          // keys per LDS tile
-constexpr int AROW = 64 + 8;     // padded LDS row (bf16)
-
-__global__ __launch_bounds__(256, 2) void attn_spatial_kernel(const bf16_t* __restrict__ q, long long ldq,
-                                                              const bf16_t* __restrict__ k, long long ldk,
-                                                              const bf16_t* __restrict__ vT, bf16_t* __restrict__ out,
-                                                              long long ldo, long long S, int heads, float scale2) {
-    __shared__ __attribute__((aligned(16))) bf16_t sK[2][AKT * AROW];
-    __shared__ __attribute__((aligned(16))) bf16_t sV[2][64 * AROW];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int qi = lane & 31, hi = lane >> 5;
-    const long long n = blockIdx.z;
-    const int h = blockIdx.y;
-    const long long C = (long long)heads * 64;
-    const long long qrow = (long long)blockIdx.x * 128 + wave * 32 + qi;
-    const bool q_ok = qrow < S;
-
-    // per-(image, head) buffer descriptors: rows / keys past S read as zeros in hardware
-    const bufrsrc_t rsQ = make_rsrc(q + n * S * ldq + h * 64, (unsigned)(((S - 1) * ldq + 64) * 2));
-    const bufrsrc_t rsK = make_rsrc(k + n * S * ldk + h * 64, (unsigned)(((S - 1) * ldk + 64) * 2));
-    const bufrsrc_t rsV = make_rsrc(vT + (n * C + h * 64) * S, (unsigned)(64 * S * 2));
-
-    bf16x8 qf[4];
-    {
-        const unsigned qoff = q_ok ? (unsigned)((qrow * ldq + hi * 8) * 2) : kInvalid;
-#pragma unroll
-        for (int st = 0; st < 4; ++st)
-            qf[st] = __builtin_bit_cast(bf16x8, buf_load16(rsQ, q_ok ? qoff + st * 32 : kInvalid));
-    }
-
-    // staging: thread owns chunks c = tid + 256*i, row = c>>3, kc = c&7
-    const int srow0 = tid >> 3, skc = tid & 7;
-    u32x4 rk[2], rv[2];
-    const int ntiles = (int)((S + AKT - 1) / AKT);
-    auto gload = [&](int t) {
-        const long long k0 = (long long)t * AKT;
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int row = srow0 + 32 * i;
-            rk[i] = buf_load16(rsK, (k0 + row < S) ? (unsigned)(((k0 + row) * ldk + skc * 8) * 2) : kInvalid);
-            rv[i] = buf_load16(rsV, (k0 + skc * 8 < S) ? (unsigned)(((long long)row * S + k0 + skc * 8) * 2) : kInvalid);
-        }
-    };
-    auto lstore = [&](int buf) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int row = srow0 + 32 * i;
-            *reinterpret_cast<u32x4*>(&sK[buf][row * AROW + skc * 8]) = rk[i];
-            *reinterpret_cast<u32x4*>(&sV[buf][row * AROW + skc * 8]) = rv[i];
-        }
-    };
-
-    f32x16 o[2];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) o[0][r] = o[1][r] = 0.f;
-    float m_run = -INFINITY, l_run = 0.f;
-
-    gload(0);
-    lstore(0);
-    __syncthreads();
-
-    for (int t = 0; t < ntiles; ++t) {
-        const int buf = t & 1;
-        if (t + 1 < ntiles) gload(t + 1);
-        const long long k0 = (long long)t * AKT;
-#pragma unroll
-        for (int sub = 0; sub < 2; ++sub) {
-            f32x16 sT;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) sT[r] = 0.f;
-#pragma unroll
-            for (int st = 0; st < 4; ++st) {
-                const bf16x8 kf = *reinterpret_cast<const bf16x8*>(&sK[buf][(sub * 32 + qi) * AROW + st * 16 + hi * 8]);
-                sT = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[st], sT, 0, 0, 0);
-            }
-            // sT[r] = score(key = sub*32 + (r&3) + 8*(r>>2) + 4*hi, query = qi)
-            float mx = -INFINITY;
-            const bool tail = (k0 + AKT > S);
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                float s = sT[r] * scale2;
-                if (tail) {
-                    const long long key = k0 + sub * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-                    if (key >= S) s = -INFINITY;
-                }
-                sT[r] = s;
-                mx = fmaxf(mx, s);
-            }
-            mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-            const float m_new = fmaxf(m_run, mx);
-            // m_new is finite from sub-tile 0 of tile 0 on (it always holds a valid key); bare v_exp_f32, see the v2 kernel
-            const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
-            float psum = 0.f;
-            float p[16];
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                p[r] = __builtin_amdgcn_exp2f(sT[r] - m_new);
-                psum += p[r];
-            }
-            l_run = l_run * alpha + psum;
-            m_run = m_new;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                o[0][r] *= alpha;
-                o[1][r] *= alpha;
-            }
-            bf16x8 pf[2];
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-                uint4 u = make_uint4(pack2bf(p[ks * 8 + 0], p[ks * 8 + 1]), pack2bf(p[ks * 8 + 2], p[ks * 8 + 3]),
-                                     pack2bf(p[ks * 8 + 4], p[ks * 8 + 5]), pack2bf(p[ks * 8 + 6], p[ks * 8 + 7]));
-                pf[ks] = __builtin_bit_cast(bf16x8, u);
-            }
-#pragma unroll
-            for (int db = 0; db < 2; ++db) {
-#pragma unroll
-                for (int ks = 0; ks < 2; ++ks) {
-                    const bf16_t* vp = &sV[buf][(db * 32 + qi) * AROW + sub * 32 + ks * 16 + hi * 4];
-                    const uint2 lo = *reinterpret_cast<const uint2*>(vp);
-                    const uint2 hi2 = *reinterpret_cast<const uint2*>(vp + 8);
-                    const bf16x8 vf = __builtin_bit_cast(bf16x8, make_uint4(lo.x, lo.y, hi2.x, hi2.y));
-                    o[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf[ks], o[db], 0, 0, 0);
-                }
-            }
-        }
-        if (t + 1 < ntiles) lstore(buf ^ 1);
-        __syncthreads();
-    }
-
-    const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
-    const float inv = 1.0f / l_tot;
-    if (q_ok) {
-        bf16_t* op = out + (n * S + qrow) * ldo + h * 64;
-#pragma unroll
-        for (int db = 0; db < 2; ++db) {
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int d0 = db * 32 + 8 * g + 4 * hi;
-                const uint2 w = make_uint2(pack2bf(o[db][g * 4 + 0] * inv, o[db][g * 4 + 1] * inv),
-                                           pack2bf(o[db][g * 4 + 2] * inv, o[db][g * 4 + 3] * inv));
-                *reinterpret_cast<uint2*>(op + d0) = w;
-            }
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------------------------
-// Spatial self-attention v2 (default).  Same mathematics and the same operand trick as v1 (S^T = K.Q^T so that a lane
-// owns a query column; the P.V contraction index is a key permutation applied identically to V^T), plus:
+// Spatial self-attention.  Block = 4 waves; each wave owns QG groups of 32 queries of one (image, head).  Per 32-key half
+// of a tile a wave computes S^T = K . Q^T with v_mfma_f32_32x32x16_bf16 (A = K rows from LDS, B = Q held in registers), so
+// each lane owns one query column: the row max / sum need one cross-lane exchange (lane <-> lane+32) and P^T is already in
+// B-operand position for O^T += V^T . P^T.  The contraction index of that second MFMA is a permutation of the keys that is
+// applied identically to the A operand, so no transpose or lane shuffle of P is needed.  V arrives pre-transposed ([C][S],
+// produced directly by the value projection GEMM).  Further:
 //   * K / V^T tiles arrive by LDS-DMA (global_load_lds_dwordx4) into a 3-deep ring, counted vmcnt, one barrier per tile;
 //   * 128-byte LDS rows with the 16-byte chunk position XOR-swizzled by (row >> 1) & 7 (on the DMA source address):
 //     every ds_read_b128 group of the K and the V^T fragment reads hits 16 distinct slots;
@@ -174,27 +21,24 @@ __global__ __launch_bounds__(256, 2) void attn_spatial_kernel(const bf16_t* __re
 //   * one softmax update per 64-key tile (not per 32), O rescale skipped when no running max moved in the wave.
 // ------------------------------------------------------------------------------------------------------
 
-// round 5 (profiles/r05_attn_ab.txt, same-process A/B): deferred maximum + no SLP packing of the softmax arithmetic (v3d_amd/build.py FILE_FLAGS:
-// v_pk_mul_f32 / v_pk_add_f32 beside MFMAs cost more than the scalar pairs they replace) 917 -> 874 us at S = 4096, 133.6 -> 128.1 us at S = 1024
-#ifndef ATTN_DEFER_MAX
-#define ATTN_DEFER_MAX 8
-#endif
-// round 6: the softmax loop is VALU-bound (per score and lane: v_fma 4 + v_exp_f32 16 + v_add 4 + v_max 4 + half a v_cvt_pk 2 = 30 cycles of the SIMD's
-// vector ALU against 16 cycles of its matrix pipe), so two of those go away:
-//   * Q is scaled by scale * log2(e) ONCE, when its fragments are loaded (re-rounded to bf16: 2^-9 relative per element, below the bf16 rounding of P),
-//     and the score accumulators start at -m_run instead of 0: the MFMAs deliver s' - m_run, and while the running maximum stands (the deferred
-//     maximum: nearly every tile after the first) the weight is a bare v_exp_f32 of the accumulator - no v_fma per score;
+// The softmax runs in the exp2 domain on bare v_exp_f32 (libm's exp2f wraps every v_exp_f32 in a denormal-range compare / select /
+// ldexp: ~6 extra VALU per score).  It is VALU-bound (per score and lane: v_fma 4 + v_exp_f32 16 + v_add 4 + v_max 4 + half a
+// v_cvt_pk 2 = 30 cycles of the SIMD's vector ALU against 16 cycles of its matrix pipe), so:
+//   * deferred maximum: a running maximum that a tile raises by at most kDeferMax (log2 units) keeps its old value - the tile's
+//     weights are then at most 2^kDeferMax (exact in fp32 / bf16 alike: the format is scale-free) and alpha = 1, so the rescale of
+//     O^T, which some lane of a 128-query wave would trigger on almost every one of the 64 tiles at S = 4096, runs only while the
+//     first tiles settle.  O / l is the same quotient either way;
+//   * Q is scaled by scale * log2(e) ONCE, when its fragments are loaded (re-rounded to bf16: 2^-9 relative per element, below the
+//     bf16 rounding of P), and the score accumulators start at -m_run instead of 0: the MFMAs deliver s' - m_run, and while the
+//     running maximum stands (nearly every tile after the first) the weight is a bare v_exp_f32 of the accumulator - no v_fma per score;
 //   * the tile maximum is gathered with v_max3_f32 (two scores per instruction).
-// A tile that raises the maximum by more than 2^ATTN_DEFER_MAX takes the wave-uniform slow path (one v_sub per score), as does tile 0.
-#ifndef ATTN_FUSE_MAX
-#define ATTN_FUSE_MAX 1
-#endif
-// round 6: inside a tile the P.V MFMAs of the first 32-key half run beside the exponentials of the second half (one scheduling region, the interleave fixed with
-// sched_group_barrier: a wave's own MFMAs hide a few VALU / transcendental issues each) instead of "all exponentials, then all MFMAs".  Same arithmetic, same order
-// of every accumulation: bit-identical results.  0 = the sequential form (A/B).
-#ifndef ATTN_PIPE
-#define ATTN_PIPE 1
-#endif
+// A tile that raises the maximum by more than kDeferMax takes the wave-uniform slow path (one v_sub per score), as does tile 0.
+// On the fast path the P.V MFMAs of the first 32-key half run beside the exponentials of the second half (one scheduling region, the
+// interleave fixed with sched_group_barrier: a wave's own MFMAs hide a few VALU / transcendental issues each).  Same arithmetic, same
+// order of every accumulation as "all exponentials, then all MFMAs": bit-identical results.
+// (profiles/r05_attn_ab.txt: deferred maximum + no SLP packing of the softmax arithmetic, v3d_amd/build.py FILE_FLAGS, 917 -> 874 us at
+// S = 4096, 133.6 -> 128.1 us at S = 1024)
+constexpr int kDeferMax = 8;
 
 // RAG (ragged token count, v3d_attn_spatial_ld): any S >= 1, V^T rows at their own stride ldv (a multiple of 8, >= S; ignored when RAG is
 // false, where the stride is S).  Keys >= S are masked twice in the last tile: their scores are -inf (as for any S) and their V^T lanes are
@@ -228,18 +72,17 @@ __global__ __launch_bounds__(256, 2) void attn_spatial_v2_kernel(const bf16_t* _
         for (int st = 0; st < 4; ++st)
             qf[g][st] = __builtin_bit_cast(bf16x8, buf_load16(rsQ, qrow < S ? (unsigned)((qrow * ldq + hi * 8 + st * 16) * 2) : kInvalid));
     }
-    if (ATTN_FUSE_MAX) {      // scores come out of the MFMAs in the exp2 domain
+    // scores come out of the MFMAs in the exp2 domain
 #pragma unroll
-        for (int g = 0; g < QG; ++g)
+    for (int g = 0; g < QG; ++g)
 #pragma unroll
-            for (int st = 0; st < 4; ++st) {
-                const u32x4 u = __builtin_bit_cast(u32x4, qf[g][st]);
-                u32x4 w;
+        for (int st = 0; st < 4; ++st) {
+            const u32x4 u = __builtin_bit_cast(u32x4, qf[g][st]);
+            u32x4 w;
 #pragma unroll
-                for (int e = 0; e < 4; ++e) w[e] = pack2bf(bflo(u[e]) * scale2, bfhi(u[e]) * scale2);
-                qf[g][st] = __builtin_bit_cast(bf16x8, w);
-            }
-    }
+            for (int e = 0; e < 4; ++e) w[e] = pack2bf(bflo(u[e]) * scale2, bfhi(u[e]) * scale2);
+            qf[g][st] = __builtin_bit_cast(bf16x8, w);
+        }
 
     // ---- LDS-DMA sources: piece = 8 rows x 128 B; lane l -> row (l >> 3), chunk position (l & 7), logical chunk pos ^ swz.
     //      Raw buffer loads to LDS with the whole byte offset in a VGPR that advances by a constant per tile (one v_add per piece):
@@ -337,8 +180,8 @@ __global__ __launch_bounds__(256, 2) void attn_spatial_v2_kernel(const bf16_t* _
         f32x16 sT[QG][2];
 #pragma unroll
         for (int g = 0; g < QG; ++g) {
-            // (fused form: the accumulators start at -m_run, finite from tile 1 on)
-            const float init = (ATTN_FUSE_MAX && t > 0) ? -m_run[g] : 0.f;
+            // (the accumulators start at -m_run, finite from tile 1 on)
+            const float init = t > 0 ? -m_run[g] : 0.f;
 #pragma unroll
             for (int sub = 0; sub < 2; ++sub)
 #pragma unroll
@@ -365,91 +208,36 @@ __global__ __launch_bounds__(256, 2) void attn_spatial_v2_kernel(const bf16_t* _
                     for (int r = 0; r < 16; ++r)
                         if ((k0 + sub * 32 + 16 * (r >> 3) + 8 * hi + (r & 7)) >= S) sT[g][sub][r] = -INFINITY;
         }
-        if (ATTN_FUSE_MAX) {
-            // sT = s' - base in the exp2 domain (base = m_run, 0 on tile 0).  d = what the running maximum grows by (0 while it stands)
-            float d[QG];
-            bool need_any = false;
+        {   // (this scope bounds the live ranges of d / need_any; without it the QG = 2 instances spill)
+        // sT = s' - base in the exp2 domain (base = m_run, 0 on tile 0).  d = what the running maximum grows by (0 while it stands)
+        float d[QG];
+        bool need_any = false;
 #pragma unroll
-            for (int g = 0; g < QG; ++g) {
-                float mx = fmaxf(sT[g][0][0], sT[g][1][0]);
+        for (int g = 0; g < QG; ++g) {
+            float mx = fmaxf(sT[g][0][0], sT[g][1][0]);
 #pragma unroll
-                for (int r = 1; r < 16; ++r) mx = __builtin_fmaxf(__builtin_fmaxf(mx, sT[g][0][r]), sT[g][1][r]);        // (v_max3_f32)
-                mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-                const bool need = (t == 0) || mx > (float)ATTN_DEFER_MAX;       // (every tile holds >= 1 valid key: mx is finite)
-                d[g] = need ? mx : 0.f;
-                alpha[g] = t == 0 ? 0.f : __builtin_amdgcn_exp2f(-d[g]);        // (tile 0: o = l = 0)
-                any_rescale |= need;
-                need_any |= need;
-                m_run[g] = (t == 0 ? 0.f : m_run[g]) + d[g];
-            }
-            const bool slow = __any(need_any);
-            if (ATTN_PIPE && !slow) {
-                // fast path (the running maxima stand: alpha = 1, no rescale): weights of half 0, then { P.V of half 0 | weights of half 1 }, then P.V of half 1
-                float psum[QG];
-                auto weights = [&](auto sub_) __attribute__((always_inline)) {
-                    constexpr int sub = decltype(sub_)::value;
+            for (int r = 1; r < 16; ++r) mx = __builtin_fmaxf(__builtin_fmaxf(mx, sT[g][0][r]), sT[g][1][r]);        // (v_max3_f32)
+            mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+            const bool need = (t == 0) || mx > (float)kDeferMax;       // (every tile holds >= 1 valid key: mx is finite)
+            d[g] = need ? mx : 0.f;
+            alpha[g] = t == 0 ? 0.f : __builtin_amdgcn_exp2f(-d[g]);        // (tile 0: o = l = 0)
+            any_rescale |= need;
+            need_any |= need;
+            m_run[g] = (t == 0 ? 0.f : m_run[g]) + d[g];
+        }
+        const bool slow = __any(need_any);
+        if (!slow) {
+            // fast path (the running maxima stand: alpha = 1, no rescale): weights of half 0, then { P.V of half 0 | weights of half 1 }, then P.V of half 1
+            float psum[QG];
+            auto weights = [&](auto sub_) __attribute__((always_inline)) {
+                constexpr int sub = decltype(sub_)::value;
 #pragma unroll
-                    for (int g = 0; g < QG; ++g) {
-                        float pv[16];
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) pv[r] = __builtin_amdgcn_exp2f(sT[g][sub][r]);
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) psum[g] += pv[r];
-#pragma unroll
-                        for (int ks = 0; ks < 2; ++ks) {
-                            const u32x4 u = {pack2bf(pv[ks * 8 + 0], pv[ks * 8 + 1]), pack2bf(pv[ks * 8 + 2], pv[ks * 8 + 3]),
-                                             pack2bf(pv[ks * 8 + 4], pv[ks * 8 + 5]), pack2bf(pv[ks * 8 + 6], pv[ks * 8 + 7])};
-                            pf[g][sub][ks] = __builtin_bit_cast(bf16x8, u);
-                        }
-                    }
-                };
-                auto pv_half = [&](auto sub_) __attribute__((always_inline)) {
-                    constexpr int sub = decltype(sub_)::value;
-#pragma unroll
-                    for (int ks = 0; ks < 2; ++ks) {
-                        const int ch = ((sub * 4 + ks * 2 + hi) ^ vsw) * 16;
-#pragma unroll
-                        for (int db = 0; db < 2; ++db) {
-                            const bf16x8 vf = *reinterpret_cast<const bf16x8*>(sb + voff[db] + ch);
-#pragma unroll
-                            for (int g = 0; g < QG; ++g) o[g][db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf[g][sub][ks], o[g][db], 0, 0, 0);
-                        }
-                    }
-                };
-#pragma unroll
-                for (int g = 0; g < QG; ++g) psum[g] = 0.f;
-                weights(std::integral_constant<int, 0>{});
-                __builtin_amdgcn_sched_barrier(0);
-                pv_half(std::integral_constant<int, 0>{});
-                weights(std::integral_constant<int, 1>{});
-                // 4 QG MFMAs beside 16 QG exponentials + 16 QG adds + 8 QG conversions: one MFMA, (every other one) a V^T fragment read, then its share of the vector work
-#pragma unroll
-                for (int i = 0; i < 4 * QG; ++i) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                    if (i % QG == 0) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x402, 10, 0);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-                pv_half(std::integral_constant<int, 1>{});
-#pragma unroll
-                for (int g = 0; g < QG; ++g) l_run[g] += psum[g];
-                continue;
-            }
-#pragma unroll
-            for (int g = 0; g < QG; ++g) {
-                float psum = 0.f;
-#pragma unroll
-                for (int sub = 0; sub < 2; ++sub) {
+                for (int g = 0; g < QG; ++g) {
                     float pv[16];
-                    if (slow) {
 #pragma unroll
-                        for (int r = 0; r < 16; ++r) pv[r] = __builtin_amdgcn_exp2f(sT[g][sub][r] - d[g]);
-                    } else {
+                    for (int r = 0; r < 16; ++r) pv[r] = __builtin_amdgcn_exp2f(sT[g][sub][r]);
 #pragma unroll
-                        for (int r = 0; r < 16; ++r) pv[r] = __builtin_amdgcn_exp2f(sT[g][sub][r]);
-                    }
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) psum += pv[r];
+                    for (int r = 0; r < 16; ++r) psum[g] += pv[r];
 #pragma unroll
                     for (int ks = 0; ks < 2; ++ks) {
                         const u32x4 u = {pack2bf(pv[ks * 8 + 0], pv[ks * 8 + 1]), pack2bf(pv[ks * 8 + 2], pv[ks * 8 + 3]),
@@ -457,38 +245,54 @@ __global__ __launch_bounds__(256, 2) void attn_spatial_v2_kernel(const bf16_t* _
                         pf[g][sub][ks] = __builtin_bit_cast(bf16x8, u);
                     }
                 }
-                l_run[g] = l_run[g] * alpha[g] + psum;
+            };
+            auto pv_half = [&](auto sub_) __attribute__((always_inline)) {
+                constexpr int sub = decltype(sub_)::value;
+#pragma unroll
+                for (int ks = 0; ks < 2; ++ks) {
+                    const int ch = ((sub * 4 + ks * 2 + hi) ^ vsw) * 16;
+#pragma unroll
+                    for (int db = 0; db < 2; ++db) {
+                        const bf16x8 vf = *reinterpret_cast<const bf16x8*>(sb + voff[db] + ch);
+#pragma unroll
+                        for (int g = 0; g < QG; ++g) o[g][db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf[g][sub][ks], o[g][db], 0, 0, 0);
+                    }
+                }
+            };
+#pragma unroll
+            for (int g = 0; g < QG; ++g) psum[g] = 0.f;
+            weights(std::integral_constant<int, 0>{});
+            __builtin_amdgcn_sched_barrier(0);
+            pv_half(std::integral_constant<int, 0>{});
+            weights(std::integral_constant<int, 1>{});
+            // 4 QG MFMAs beside 16 QG exponentials + 16 QG adds + 8 QG conversions: one MFMA, (every other one) a V^T fragment read, then its share of the vector work
+#pragma unroll
+            for (int i = 0; i < 4 * QG; ++i) {
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                if (i % QG == 0) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+                __builtin_amdgcn_sched_group_barrier(0x402, 10, 0);
             }
-        } else {
-        // softmax in the exp2 domain on RAW scores: p = exp2(s * scale2 - m * scale2) is one v_fma + one bare v_exp_f32 per
-        // score (libm's exp2f wraps every v_exp_f32 in a denormal-range compare / select / ldexp: ~6 extra VALU per score, and
-        // the per-score scale multiply and -inf selects were another 3 - the loop was VALU-bound on them)
+            __builtin_amdgcn_sched_barrier(0);
+            pv_half(std::integral_constant<int, 1>{});
+#pragma unroll
+            for (int g = 0; g < QG; ++g) l_run[g] += psum[g];
+            continue;
+        }
 #pragma unroll
         for (int g = 0; g < QG; ++g) {
-            float mx = -INFINITY;
-#pragma unroll
-            for (int sub = 0; sub < 2; ++sub)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) mx = fmaxf(mx, sT[g][sub][r]);
-            mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-            float m_new = fmaxf(m_run[g], mx);                // raw-score domain; every tile holds >= 1 valid key, so finite
-            // deferred maximum (ATTN_DEFER_MAX > 0): a running maximum that grew by less than 2^ATTN_DEFER_MAX keeps its old value - the
-            // tile's weights are then at most 2^ATTN_DEFER_MAX (exact in fp32 / bf16 alike: the format is scale-free) and alpha = 1, so the
-            // 128-multiply rescale of O^T below, which some lane of a 128-query wave triggers on almost every one of the 64 tiles at
-            // S = 4096, runs only while the first tiles settle.  O / l is the same quotient either way.  (-inf start: the difference is +inf)
-            if (ATTN_DEFER_MAX > 0 && (m_new - m_run[g]) * scale2 <= (float)ATTN_DEFER_MAX) m_new = m_run[g];
-            alpha[g] = __builtin_amdgcn_exp2f((m_run[g] - m_new) * scale2);   // first tile: exp2(-inf) = 0 on o = l = 0
-            any_rescale |= (alpha[g] != 1.f);
-            const float mb = -m_new * scale2;
             float psum = 0.f;
 #pragma unroll
             for (int sub = 0; sub < 2; ++sub) {
                 float pv[16];
+                if (slow) {
 #pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    pv[r] = __builtin_amdgcn_exp2f(__builtin_fmaf(sT[g][sub][r], scale2, mb));
-                    psum += pv[r];
+                    for (int r = 0; r < 16; ++r) pv[r] = __builtin_amdgcn_exp2f(sT[g][sub][r] - d[g]);
+                } else {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) pv[r] = __builtin_amdgcn_exp2f(sT[g][sub][r]);
                 }
+#pragma unroll
+                for (int r = 0; r < 16; ++r) psum += pv[r];
 #pragma unroll
                 for (int ks = 0; ks < 2; ++ks) {
                     const u32x4 u = {pack2bf(pv[ks * 8 + 0], pv[ks * 8 + 1]), pack2bf(pv[ks * 8 + 2], pv[ks * 8 + 3]),
@@ -497,7 +301,6 @@ __global__ __launch_bounds__(256, 2) void attn_spatial_v2_kernel(const bf16_t* _
                 }
             }
             l_run[g] = l_run[g] * alpha[g] + psum;
-            m_run[g] = m_new;
         }
         }
         if (__any(any_rescale)) {
@@ -545,11 +348,9 @@ __global__ __launch_bounds__(256, 2) void attn_spatial_v2_kernel(const bf16_t* _
 }
 
 // ------------------------------------------------------------------------------------------------------
-// Temporal self-attention (frame axis).  A "problem" is one (sample b, position s, head h): Tq x Tk scores,
-// d_head 64.  G = 64 / Tq problems share a wave; lane (slot, i) owns query frame i of its slot's problem, keeps
-// q and the output row in registers and walks the Tk keys/values staged in LDS (all lanes of a slot read the same
-// LDS address -> broadcast).  Loads follow the frame stride of the channels-last layout directly, so the
-// "(b t) s c -> (b s) t c" transposes of the reference never happen.
+// Temporal self-attention (frame axis).  A "problem" is one (sample b, position s, head h): Tq x Tk scores, d_head 64.
+// Loads follow the frame stride of the channels-last layout directly, so the "(b t) s c -> (b s) t c" transposes of the
+// reference never happen.
 // ------------------------------------------------------------------------------------------------------
 constexpr int TMAX = 32;
 
@@ -557,151 +358,12 @@ struct TP {
     const bf16_t* q; long long q_sb, q_st, q_ss;
     const bf16_t* k; const bf16_t* v; long long kv_sb, kv_st, kv_ss;
     bf16_t* out; long long o_sb, o_st, o_ss;
-    long long P, S; int heads, Tq, Tk, G; float scale;
-};
-
-__global__ __launch_bounds__(256) void attn_temporal_kernel(TP p) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int per_wave = p.G * p.Tk * 64;  // bf16 elements of K (and of V) per wave
-    bf16_t* sK = reinterpret_cast<bf16_t*>(smem_raw) + (size_t)wave * 2 * per_wave;
-    bf16_t* sV = sK + per_wave;
-
-    const long long wave_id = (long long)blockIdx.x * 4 + wave;
-    const long long p0 = wave_id * p.G;
-
-    // stage K and V rows: chunk c -> (row = c>>3, kc = c&7), row -> (slot, j).  The (b, s, h) decomposition of a slot's problem
-    // is done once by lane `slot` and fetched with two bpermutes per chunk, and the chunks go in batches of UB: all 2*UB
-    // 16-byte loads of a batch are in flight before the first LDS store (the first version divided 64-bit indices and waited
-    // for its two loads in every one of the ~7 trips: a serial load -> store chain, 194 us against 75 us of HBM time at 64x64)
-    const int nchunks = p.G * p.Tk * 8;
-    long long slot_base = -1;          // element offset of (b, t = 0, s, h) for slot `lane`
-    if (lane < p.G && p0 + lane < p.P) {
-        const long long pp = p0 + lane;
-        const int h = (int)(pp % p.heads);
-        const long long bs = pp / p.heads;
-        const long long s_ = bs % p.S, b_ = bs / p.S;
-        slot_base = b_ * p.kv_sb + s_ * p.kv_ss + h * 64;
-    }
-    constexpr int UB = 4;
-    for (int c0 = 0; c0 < nchunks; c0 += 64 * UB) {
-        uint4 uk[UB], uv[UB];
-#pragma unroll
-        for (int u = 0; u < UB; ++u) {
-            const int c = c0 + u * 64 + lane;
-            const int row = c >> 3, kc = c & 7;
-            const int slot_ = (int)((unsigned)row / (unsigned)p.Tk), j = row - slot_ * p.Tk;
-            const int src_lane = slot_ < 64 ? slot_ : 0;
-            const unsigned lo = (unsigned)__shfl((int)(unsigned)(slot_base & 0xffffffffll), src_lane, 64);
-            const int hi = __shfl((int)(slot_base >> 32), src_lane, 64);
-            const long long base = ((long long)hi << 32) | lo;
-            uk[u] = make_uint4(0, 0, 0, 0);
-            uv[u] = uk[u];
-            if (c < nchunks && base >= 0) {
-                const long long off = base + (long long)j * p.kv_st + kc * 8;
-                uk[u] = *reinterpret_cast<const uint4*>(p.k + off);
-                uv[u] = *reinterpret_cast<const uint4*>(p.v + off);
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < UB; ++u) {
-            const int c = c0 + u * 64 + lane;
-            if (c < nchunks) {
-                *reinterpret_cast<uint4*>(sK + (c >> 3) * 64 + (c & 7) * 8) = uk[u];
-                *reinterpret_cast<uint4*>(sV + (c >> 3) * 64 + (c & 7) * 8) = uv[u];
-            }
-        }
-    }
-    __syncthreads();
-
-    const int slot = lane / p.Tq, i = lane - slot * p.Tq;
-    const long long pp = p0 + slot;
-    if (slot >= p.G || pp >= p.P) return;
-    const int h = (int)(pp % p.heads);
-    const long long bs = pp / p.heads;
-    const long long s = bs % p.S, b = bs / p.S;
-
-    // q stays packed (32 bf16 pairs); scores by v_dot2c_f32_bf16 (2 MACs per instruction, no unpacking), P rounded to bf16
-    // pairs and P.V by dot2 over key pairs with the two V rows interleaved by v_perm_b32: ~1800 VALU per lane instead of
-    // ~4700 (shift/and unpack + fma per element) - the kernel was VALU-bound at 2.5x its HBM time
-    typedef __bf16 bf16x2v __attribute__((ext_vector_type(2)));
-    uint32_t qp[32];
-    {
-        const bf16_t* qptr = p.q + b * p.q_sb + (long long)i * p.q_st + s * p.q_ss + h * 64;
-#pragma unroll
-        for (int c = 0; c < 8; ++c) {
-            const uint4 u = *reinterpret_cast<const uint4*>(qptr + c * 8);
-            qp[c * 4 + 0] = u.x; qp[c * 4 + 1] = u.y; qp[c * 4 + 2] = u.z; qp[c * 4 + 3] = u.w;
-        }
-    }
-    const bf16_t* kk = sK + slot * p.Tk * 64;
-    const bf16_t* vv = sV + slot * p.Tk * 64;
-    auto dot2 = [](uint32_t a_, uint32_t b_, float c_) __attribute__((always_inline)) {
-        return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2v, a_), __builtin_bit_cast(bf16x2v, b_), c_, false);
-    };
-    float sc[TMAX];
-    float mx = -INFINITY;
-#pragma unroll
-    for (int j = 0; j < TMAX; ++j) {
-        sc[j] = -INFINITY;
-        if (j < p.Tk) {
-            float a0 = 0.f, a1 = 0.f;
-#pragma unroll
-            for (int c = 0; c < 8; ++c) {
-                const uint4 u = *reinterpret_cast<const uint4*>(kk + j * 64 + c * 8);
-                a0 = dot2(qp[c * 4 + 0], u.x, a0);
-                a1 = dot2(qp[c * 4 + 1], u.y, a1);
-                a0 = dot2(qp[c * 4 + 2], u.z, a0);
-                a1 = dot2(qp[c * 4 + 3], u.w, a1);
-            }
-            sc[j] = (a0 + a1) * p.scale;
-            mx = fmaxf(mx, sc[j]);
-        }
-    }
-    float ov[64];
-#pragma unroll
-    for (int d = 0; d < 64; ++d) ov[d] = 0.f;
-    float l = 0.f;
-    const float mxl = mx * 1.44269504088896340736f;
-#pragma unroll
-    for (int jp = 0; jp < TMAX / 2; ++jp) {
-        if (2 * jp < p.Tk) {
-            const bool two = 2 * jp + 1 < p.Tk;            // wave-uniform
-            const float p0 = __builtin_amdgcn_exp2f(__builtin_fmaf(sc[2 * jp], 1.44269504088896340736f, -mxl));
-            const float p1 = two ? __builtin_amdgcn_exp2f(__builtin_fmaf(sc[2 * jp + 1], 1.44269504088896340736f, -mxl)) : 0.f;
-            const uint32_t pp = pack2bf(p0, p1);
-            l += bflo(pp) + bfhi(pp);                      // normalise by exactly the (rounded) weights that are applied
-            const bf16_t* v0 = vv + (2 * jp) * 64;
-            const bf16_t* v1 = two ? v0 + 64 : v0;         // (weight 0 on the duplicate row)
-#pragma unroll
-            for (int c = 0; c < 8; ++c) {
-                const uint4 ua = *reinterpret_cast<const uint4*>(v0 + c * 8);
-                const uint4 ub = *reinterpret_cast<const uint4*>(v1 + c * 8);
-                const uint32_t wa[4] = {ua.x, ua.y, ua.z, ua.w}, wb[4] = {ub.x, ub.y, ub.z, ub.w};
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const uint32_t lo = __builtin_amdgcn_perm(wb[e], wa[e], 0x05040100u);   // (v[j][d], v[j+1][d]),  d = c*8 + 2e
-                    const uint32_t hi = __builtin_amdgcn_perm(wb[e], wa[e], 0x07060302u);   // d + 1
-                    ov[c * 8 + 2 * e] = dot2(pp, lo, ov[c * 8 + 2 * e]);
-                    ov[c * 8 + 2 * e + 1] = dot2(pp, hi, ov[c * 8 + 2 * e + 1]);
-                }
-            }
-        }
-    }
-    const float inv = 1.0f / l;
-    bf16_t* op = p.out + b * p.o_sb + (long long)i * p.o_st + s * p.o_ss + h * 64;
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-        const uint4 w = make_uint4(pack2bf(ov[c * 8 + 0] * inv, ov[c * 8 + 1] * inv), pack2bf(ov[c * 8 + 2] * inv, ov[c * 8 + 3] * inv),
-                                   pack2bf(ov[c * 8 + 4] * inv, ov[c * 8 + 5] * inv), pack2bf(ov[c * 8 + 6] * inv, ov[c * 8 + 7] * inv));
-        *reinterpret_cast<uint4*>(op + c * 8) = w;
-    }
-}
+    long long P, S; int heads, Tq, Tk, G; float scale;   // G = 1: read by no kernel, but dropping it shifts the kernarg layout and
+};                                                        // re-allocates the scalar registers of attn_temporal_mfma_kernel
 
 // ------------------------------------------------------------------------------------------------------
-// Temporal self-attention on the matrix cores (round 5).  One wave per problem (sample b, position s, head h): T <= 32 frames, d_head 64.
-// The VALU kernel above spends ~2400 issue cycles per problem on dot2 arithmetic (46 us of vector ALU beside 75 us of HBM time at the 64 x 64
-// level, 2.8 TB/s measured); here the two contractions are 16 x 16 x 32 MFMAs on operands that need no repacking:
+// Temporal self-attention on the matrix cores, Tq, Tk <= 32 frames.  One wave per problem.  The two contractions are 16 x 16 x 32 MFMAs
+// on operands that need no repacking:
 //   S^T = K Q^T    A = K rows, B = Q rows: a lane (row = lane & 15, k-group g = lane >> 4) loads 16 bytes of frame `row` at channel
 //                  32 ks + 8 g - 64 contiguous bytes per frame per instruction, whole 128-byte lines over the two k steps, straight from HBM
 //                  into the operand registers (the frame stride of the channels-last layout is the row stride: no transpose, no staging).
@@ -711,7 +373,7 @@ __global__ __launch_bounds__(256) void attn_temporal_kernel(TP p) {
 //                  eight probabilities it already holds (rounded to bf16 pairs), no lane exchange; the A operand V^T[d][slot] is gathered from
 //                  the wave's LDS copy of V (rows padded to 144 bytes: the four k-groups read four different 32-byte bank groups).
 //                  C: lane (query i, g) holds channels 16 dt + 4 g + r: an 8-byte store per (query tile, channel tile).
-// P is rounded to bf16 and the row is normalised by the sum of the ROUNDED weights, exactly as the VALU kernel (and the emulator) do.
+// P is rounded to bf16 and the row is normalised by the sum of the ROUNDED weights, exactly as the emulator does.
 // ------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void attn_temporal_mfma_kernel(TP p) {
     constexpr int VP = 72;                                  // LDS row pitch of V in bf16 (144 bytes)
@@ -1012,17 +674,8 @@ extern "C" int v3d_attn_spatial(const void* q, int64_t ldq, const void* k, int64
     V3D_REQUIRE((((uintptr_t)q | (uintptr_t)k | (uintptr_t)vT) & 15) == 0 && ((uintptr_t)out & 7) == 0, "v3d_attn_spatial: misaligned pointer");
     V3D_REQUIRE((unsigned long long)(S + 192) * (ldq > ldk ? ldq : ldk) * 2ull <= kMaxBufBytes && (unsigned long long)(64 * S + 256) * 2ull <= kMaxBufBytes,
                 "v3d_attn_spatial: per-image q / k / v slab exceeds 4 GiB");
-    static int impl = -1;
-    if (impl < 0) {
-        const char* e = getenv("V3D_ATTN_IMPL");
-        impl = e ? atoi(e) : 2;
-    }
     const float sc2 = scale * 1.44269504088896340736f;
-    if (impl == 1) {
-        dim3 grid((unsigned)((S + 127) / 128), (unsigned)heads, (unsigned)n_img);
-        hipLaunchKernelGGL(attn_spatial_kernel, grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)q, (long long)ldq,
-                           (const bf16_t*)k, (long long)ldk, (const bf16_t*)vT, (bf16_t*)out, (long long)ldo, (long long)S, heads, sc2);
-    } else if (S >= 1024 && impl != 3) {
+    if (S >= 1024) {
         dim3 grid((unsigned)((S + 255) / 256), (unsigned)heads, (unsigned)n_img);
         hipLaunchKernelGGL((attn_spatial_v2_kernel<2, false>), grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)q, (long long)ldq,
                            (const bf16_t*)k, (long long)ldk, (const bf16_t*)vT, (bf16_t*)out, (long long)ldo, (long long)S, heads, sc2, (long long)S);
@@ -1073,38 +726,16 @@ extern "C" int v3d_attn_temporal(const void* q, int64_t q_sb, int64_t q_st, int6
     p.k = (const bf16_t*)k; p.v = (const bf16_t*)v; p.kv_sb = kv_sb; p.kv_st = kv_st; p.kv_ss = kv_ss;
     p.out = (bf16_t*)out; p.o_sb = o_sb; p.o_st = o_st; p.o_ss = o_ss;
     p.P = (long long)B * S * heads; p.S = S; p.heads = heads; p.Tq = Tq; p.Tk = Tk; p.scale = scale;
+    p.G = 1;
     if (Tq > TMAX || Tk > TMAX) {
-        p.G = 1;
         const long long waves = p.P * ((Tq + 31) / 32);     // one wave per (problem, 32-query tile)
         const long long blocks = (waves + 3) / 4;
         V3D_REQUIRE(blocks < (1ll << 31), "v3d_attn_temporal: grid too large");
         hipLaunchKernelGGL(attn_temporal_long_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p);
-        return v3d_check_launch("v3d_attn_temporal");
-    }
-    static int timpl = -1;
-    if (timpl < 0) {
-        const char* e = getenv("V3D_ATTN_TEMPORAL_IMPL");   // A/B knob (Tq, Tk <= 32): 1 = the VALU (dot2) kernel of rounds 1-4, 2 = the MFMA kernel (default)
-        timpl = e ? atoi(e) : 2;
-    }
-    if (timpl != 1) {
-        p.G = 1;
+    } else {
         const long long blocks = (p.P + 3) / 4;             // one wave per problem
         V3D_REQUIRE(blocks < (1ll << 31), "v3d_attn_temporal: grid too large");
         hipLaunchKernelGGL(attn_temporal_mfma_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p);
-        return v3d_check_launch("v3d_attn_temporal");
     }
-    {   // problems per wave: as many Tq-lane slots as fit in a wave, capped so K+V staging stays <= 16 KiB per wave
-        int g = 64 / Tq;
-        const int cap = 16384 / (Tk * 256);
-        if (g > cap) g = cap;
-        if (g < 1) g = 1;
-        p.G = g;
-    }
-    const long long nwaves = (p.P + p.G - 1) / p.G;
-    const long long blocks = (nwaves + 3) / 4;
-    V3D_REQUIRE(blocks < (1ll << 31), "v3d_attn_temporal: grid too large");
-    const size_t shmem = (size_t)4 * 2 * p.G * Tk * 64 * sizeof(bf16_t);
-    V3D_REQUIRE(shmem <= 64 * 1024, "v3d_attn_temporal: LDS request %zu too large", shmem);
-    hipLaunchKernelGGL(attn_temporal_kernel, dim3((unsigned)blocks), dim3(256), shmem, (hipStream_t)stream, p);
     return v3d_check_launch("v3d_attn_temporal");
 }

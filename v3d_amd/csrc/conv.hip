@@ -19,26 +19,11 @@
 //     pairs that would cross an image boundary inside the flat pixel order read their fragment from a zero page instead.
 // L2 -> LDS fill per chunk and CU drops from 9 x 12 KiB (activations) + 180 KiB (weights) to 23 + 180 KiB, the GroupNorm apply pass and
 // its 2 x 94 MB of HBM traffic per use disappear.
-#include <stdlib.h>
-
-#define E4_ASM_READS 0        // this file chooses the epilogue's LDS read form per kernel (CONV_TEMP_READS below); gn_flush keeps the compiler-visible reads
+#define E4_ASM_READS 0        // this file chooses the epilogue's LDS read form per kernel (kConvTempReads below); gn_flush keeps the compiler-visible reads
 #include "gemm_common.h"
 
-#ifndef CONV_3X3_READS
-#define CONV_3X3_READS 0       // ... of the 3 x 3 haloed kernels: measured -1 ... +6 % per launch with the lean asm form (2), see the call
-#endif
-#ifndef CONV_TEMP_READS
-#define CONV_TEMP_READS 2      // e4_fragment read form of the temporal haloed kernels (A/B: -DCONV_TEMP_READS=0)
-#endif
-
-// Timing experiments (tools/conv_ablate.sh, results in profiles/r03_conv_ablation.txt): -DCONV_ABL=<bits> builds of this file only -
-// compile-time, so the measured loop carries no extra branches.  1 no epilogue, 2 no MFMA, 4 no weight DMA, 4096 no fragment reads,
-// 8192 no halo DMA, 16384 no normalisation chain, 32768 no per-step waits / barrier, 65536 halo source rows folded into an L2-resident window.
-// The product build has CONV_ABL = 0.
-#ifndef CONV_ABL
-#define CONV_ABL 0
-#endif
-#define CABL(bit) ((CONV_ABL & (bit)) != 0)
+constexpr int kConv3x3Reads = 0;      // e4_fragment read form of the 3 x 3 haloed kernels: measured -1 ... +6 % per launch with the lean asm form (2), see the call
+constexpr int kConvTempReads = 2;     // ... of the temporal haloed kernels
 // (round 4 A/B'ed the placement of this loop's pieces - weight DMA inside the MFMA sequence, halo behind the weights, odd waves' DMA in front of
 // their reads, no s_setprio: all neutral or slower, profiles/r04_mainloop_ab.txt; the variants are in profiles/r04_mainloop_variants.patch)
 
@@ -51,11 +36,7 @@ struct HaloGeom {
     static constexpr int BM = 192, BN = 320;
     static constexpr int NT = HM == HM_CONV ? 9 : 3;                                  // taps = steps per 32-channel chunk
     static constexpr int LINE = HM == HM_CONV ? ((W_ + 2 + 7) / 8) * 8 : 32;          // halo pixels per line (image row / frame)
-    // W = 8 (round 6): a tile is three WHOLE 8 x 8 images, so the lines above and below it belong to other images and are never read (the
-    // taps that would are masked to the zero page): the halo holds the tile's 24 lines only (TOP = 0) and up to three statistics groups
-    static constexpr int TOP = HM == HM_CONV && W_ == 8 ? 0 : 1;                      // halo lines above the tile's first line
-    static constexpr int NSTAT = HM == HM_CONV && W_ == 8 ? 3 : 2;                    // statistics groups (images) a halo can touch
-    static constexpr int NLINES = HM == HM_CONV ? BM / W_ + 2 * TOP : 8;              // 3x3: tile rows + 2; temporal: 6 frames + 2
+    static constexpr int NLINES = HM == HM_CONV ? BM / W_ + 2 : 8;                    // 3x3: tile rows + 2; temporal: 6 frames + 2
     static constexpr int HROWS = NLINES * LINE;
     static constexpr int HPW = ((HROWS + 15) / 16 + 7) / 8;                           // 1-KiB halo pieces per wave
     static constexpr int HBYTES = HPW * 8 * 1024;
@@ -135,7 +116,7 @@ __global__ __launch_bounds__(512, 2) void conv_halo_kernel(GP p, int ntiles) {
     constexpr int WM = 96, WN = 80, MF = 6, NF = 5;
     constexpr int WSTAGE = BN * ROWB;                     // 20 KiB of weights per (chunk, tap) step
     constexpr int EPI_REGION = 16 * (NF * 32 + 16);
-    constexpr int TABB = G::NSTAT * 256;                 // (scale, shift) of a chunk's 32 channels for each statistics group of the halo
+    constexpr int TABB = 2 * 256;                        // (scale, shift) of a chunk's 32 channels for each of the two statistics groups of the halo
     constexpr int RING_OFF = 0, HALO_OFF = NS * WSTAGE, ZERO_OFF = HALO_OFF + NBUF * HBYTES, TAB_OFF = ZERO_OFF + 1024,
                   EPI_OFF = TAB_OFF + NW * TABB * G::NTAB, SK_OFF = EPI_OFF + NW * EPI_REGION;
     __shared__ __attribute__((aligned(1024))) unsigned char lds[SK_OFF + SK_TAB_BYTES];        // the ONLY __shared__ object
@@ -189,7 +170,6 @@ __global__ __launch_bounds__(512, 2) void conv_halo_kernel(GP p, int ntiles) {
         w_c1 = q.u1;
     };
     auto issue_w_piece = [&](int stage, int ltap, int i) __attribute__((always_inline)) {
-        if (CABL(4)) return;
         // scalar offset: tap, chunk and the piece's 16-row block (N % 320 == 0: every row of the tile exists)
         const int so = (int)(ltap * tap_bytes) + w_c * 64 + (w_n0 / 16 + wave + NW * i) * row16_bytes;
         if (i < 2 || grp == 0)
@@ -211,11 +191,10 @@ __global__ __launch_bounds__(512, 2) void conv_halo_kernel(GP p, int ntiles) {
         int live;          // the cursor is inside this block's tiles
         int fr0;           // 3x3: first flat image row of the tile;  temporal: sample * T + first frame of the tile's frame block
         int frB;           // 3x3: first flat image row of the halo's SECOND statistics group (image);  temporal: position block * 32
-        int frC;           // 3x3, W = 8: first flat image row of the halo's THIRD statistics group
         unsigned statA;    // (scale, shift) rows of the halo's first / last source row
         unsigned statB;
     };
-    HTile ht = {0, 0, 0, 0, 0u, 0u}, xt = {0, 0, 0, 0, 0u, 0u};      // cursor's tile / the tile of the image issued last (picked up by its normalisation chain)
+    HTile ht = {0, 0, 0, 0u, 0u}, xt = {0, 0, 0, 0u, 0u};      // cursor's tile / the tile of the image issued last (picked up by its normalisation chain)
     int h_tab = 0, x_tab = 0;                             // table slot the next issue fills / the last issue filled
     unsigned latch_base = 0;
     // piece i of this wave = halo pixel rows (wave + 8 i) * 16 .. + 15; the lane holds 16 bytes of pixel row + (lane >> 2).  Pieces start at
@@ -235,18 +214,16 @@ __global__ __launch_bounds__(512, 2) void conv_halo_kernel(GP p, int ntiles) {
         if (HM == HM_CONV) {
             const int fr0 = tm * (BM / W_);                                    // first flat image row of the tile
             const int nfr = (int)(p.M / W_);
-            const int f_lo = fr0 - G::TOP < 0 ? 0 : fr0 - G::TOP, f_hi = fr0 + BM / W_ - 1 + G::TOP >= nfr ? nfr - 1 : fr0 + BM / W_ - 1 + G::TOP;
+            const int f_lo = fr0 - 1 < 0 ? 0 : fr0 - 1, f_hi = fr0 + BM / W_ >= nfr ? nfr - 1 : fr0 + BM / W_;
             ht.fr0 = fr0;
             ht.statA = (unsigned)((long long)f_lo * W_ / rps);
             ht.statB = (unsigned)((long long)f_hi * W_ / rps);
             ht.frB = (int)(((long long)ht.statA + 1) * rps / W_);
-            ht.frC = (int)(((long long)ht.statA + 2) * rps / W_);
         } else {
             // tile row-block tm = (sample b, frame block tb, position block sb), positions fastest
             const int sb = tm % sblocks, tb = (tm / sblocks) % tblocks, b = tm / (sblocks * tblocks);
             ht.fr0 = b * p.T + tb * 6;
             ht.frB = sb * 32;
-            ht.frC = 0;
             ht.statA = ht.statB = (unsigned)(((long long)b * p.T * p.S) / rps);          // one statistics group per sample (the 3-D GroupNorm)
         }
     };
@@ -258,10 +235,10 @@ __global__ __launch_bounds__(512, 2) void conv_halo_kernel(GP p, int ntiles) {
         second = 0;
         if (HM == HM_CONV) {
             const int line = hp / LINE, x = hp - line * LINE - 1;
-            const int fr = t.fr0 - G::TOP + line;
+            const int fr = t.fr0 - 1 + line;
             const int nfr = (int)(p.M / W_);
             const bool ok = t.live && x >= 0 && x < W_ && fr >= 0 && fr < nfr && line < G::NLINES;
-            second = (fr >= t.frB ? 1 : 0) + (G::NSTAT > 2 && fr >= t.frC ? 1 : 0);       // statistics group of the line, relative to statA
+            second = fr >= t.frB ? 1 : 0;
             return ok ? (unsigned)(fr * W_ + x) : kInvalid;
         } else {
             const int line = hp >> 5, sp = hp & 31;
@@ -276,15 +253,13 @@ __global__ __launch_bounds__(512, 2) void conv_halo_kernel(GP p, int ntiles) {
         }
     };
     auto issue_halo = [&]() __attribute__((always_inline)) {
-        if (CABL(8192)) return;
         if (h_c == h_c1) set_htile(h_it);                 // (cursor at the end of its item - or at the very start: 0 == 0 - : enter item h_it)
         const bool second = h_c >= k1chunks;
         const int cc = second ? h_c - k1chunks : h_c;
         const unsigned ld2 = (unsigned)((second ? p.lda2 : p.lda) * 2);
-        if (XF && lane < 16 * G::NSTAT) {
-            // (scale, shift) of this chunk's 32 channels for the (at most NSTAT) statistics groups of the halo: NSTAT x 256 B
-            const unsigned sg = ht.statA + (unsigned)(lane >> 4);
-            const unsigned st = G::NSTAT == 2 ? (lane < 16 ? ht.statA : ht.statB) : (sg < ht.statB ? sg : ht.statB);
+        if (XF && lane < 32) {
+            // (scale, shift) of this chunk's 32 channels for the two statistics groups of the halo: 2 x 256 B
+            const unsigned st = lane < 16 ? ht.statA : ht.statB;
             const unsigned vo = (unsigned)(((long long)st * p.K + (long long)h_c * 32) * 8) + (unsigned)(lane & 15) * 16u;
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rsT, (__attribute__((address_space(3))) void*)(lds + TAB_OFF + (wave * G::NTAB + h_tab) * TABB), 16, (int)(ht.live ? vo : kInvalid), 0, 0, 0);
         }
@@ -298,7 +273,7 @@ __global__ __launch_bounds__(512, 2) void conv_halo_kernel(GP p, int ntiles) {
         for (int i = 0; i < HPW; ++i) {
             int second_stat;
             const unsigned row = halo_row(ht, i, second_stat, ln);
-            const unsigned vo = row == kInvalid ? kInvalid : (CABL(65536) ? (row & 1023u) : row) * ld2 + (unsigned)hchunkpos * 16u;     // (65536: L2-hot source rows)
+            const unsigned vo = row == kInvalid ? kInvalid : row * ld2 + (unsigned)hchunkpos * 16u;
             __builtin_amdgcn_raw_ptr_buffer_load_lds(second ? rsA2 : rsA1, (__attribute__((address_space(3))) void*)(lds + HALO_OFF + h_buf * HBYTES + (wave + NW * i) * 1024), 16,
                                                      (int)vo, cc * 64, 0, 0);
         }
@@ -308,7 +283,7 @@ __global__ __launch_bounds__(512, 2) void conv_halo_kernel(GP p, int ntiles) {
     // ---------------------------------------------------------------- the in-place normalisation of the image the loader filled last
     // image being normalised: the one issue_halo wrote at the last issue step
     unsigned xf_base = 0;                                 // LDS byte address of that image
-    HTile ct = {0, 0, 0, 0, 0u, 0u};                         // its tile
+    HTile ct = {0, 0, 0, 0u, 0u};                            // its tile
     int c_tab = 0;                                        // its table slot
     XfState xs;
     auto xf_read_vec = [&](int v) __attribute__((always_inline)) -> u32x4 {
@@ -395,12 +370,6 @@ __global__ __launch_bounds__(512, 2) void conv_halo_kernel(GP p, int ntiles) {
 #pragma unroll
         for (int j = 0; j < NF; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
     bf16x8 xf[MF], wf[NF];
-#if CONV_ABL
-#pragma unroll
-    for (int i = 0; i < MF; ++i) xf[i] = bf16x8{};      // (the "no fragment reads" timing experiment multiplies whatever is here)
-#pragma unroll
-    for (int j = 0; j < NF; ++j) wf[j] = bf16x8{};
-#endif
     const int wfrag_off = (lane & 15) * ROWB + (((lane >> 4) ^ wswz(lane & 15)) * 16) + wn * WN * ROWB;
     // activation fragment i of the wave = tile rows wm * 96 + i * 16 .. + 15 = 16 consecutive halo pixels starting at pixel row hp0(i) (a
     // multiple of 8, wave-uniform) + tap column dx.  Per-lane byte offset inside a halo image = faddr[dx] (pixel (lane & 15) + dx, chunk
@@ -409,16 +378,13 @@ __global__ __launch_bounds__(512, 2) void conv_halo_kernel(GP p, int ntiles) {
     unsigned faddr[NDX];
 #pragma unroll
     for (int dx = 0; dx < NDX; ++dx) {
-        // (W = 8: a fragment's 16 rows are two image lines of 8 pixels - lanes 8 .. 15 of a 16-lane group sit one halo line further; bit 2 of the pixel row, which
-        // the swizzle keys on, and the row's bank class mod 4 are what they would be for 16 consecutive pixels)
-        const int hp = HM == HM_CONV && W_ == 8 ? (lane & 7) + dx + ((lane >> 3) & 1) * LINE : (lane & 15) + dx;
+        const int hp = (lane & 15) + dx;
         faddr[dx] = (unsigned)(HALO_OFF + hp * 64 + (((lane >> 4) ^ hswz(hp)) * 16));
     }
     auto foff = [&](int i) __attribute__((always_inline)) -> unsigned {
         const int r = wm * WM + i * 16;
-        return (unsigned)((HM == HM_CONV ? (r / W_ + G::TOP - 1) * LINE + (r % W_) : r) * 64);      // (TOP = 0: line - 1 + dy; the dy = 0 tap of tile line 0 is masked)
+        return (unsigned)((HM == HM_CONV ? (r / W_) * LINE + (r % W_) : r) * 64);
     };
-    const bool upper_half = HM == HM_CONV && W_ == 8 && ((lane >> 3) & 1);      // W = 8: the lane's pixel is in the fragment's second image line
     const unsigned zfrag = (unsigned)(ZERO_OFF + (lane & 15) * 64 + (lane >> 4) * 16);
     int c_buf = 0;                                        // halo image of the chunk being consumed (its offset is folded into faddr)
     unsigned vmask = 0;                                   // 3x3: bit (2 i) = fragment i may use dy = 0, bit (2 i + 1) = dy = 2 (same image)
@@ -460,9 +426,8 @@ __global__ __launch_bounds__(512, 2) void conv_halo_kernel(GP p, int ntiles) {
             for (int i = 0; i < MF; ++i) {
                 const int fr = (int)(((long long)tm * BM + wm * WM + i * 16) / W_);
                 const int y = fr % H;
-                // (W = 8: the fragment is the image lines y and y + 1, y even - only its first line can lack the line above, only its second the line below)
                 vmask |= (y > 0 ? 1u : 0u) << (2 * i);
-                vmask |= (y + (W_ == 8 ? 1 : 0) < H - 1 ? 1u : 0u) << (2 * i + 1);
+                vmask |= (y < H - 1 ? 1u : 0u) << (2 * i + 1);
             }
             vmask = (unsigned)__builtin_amdgcn_readfirstlane((int)vmask);
         }
@@ -472,27 +437,24 @@ __global__ __launch_bounds__(512, 2) void conv_halo_kernel(GP p, int ntiles) {
                 constexpr int dy = HM == HM_CONV ? tap / 3 : tap, dx = HM == HM_CONV ? tap % 3 : 0;
                 constexpr int ltap = (tap + NS - 1) % NT;             // the weight loader's tap, NS-1 steps ahead
                 // ---- fragment reads of this step
-                if (!CABL(4096)) {
-                    const unsigned char* sb = lds + RING_OFF + rd * WSTAGE + wfrag_off;
-                    // (the per-fragment sums below are loop invariants the compiler would otherwise hoist out of the nine tap bodies and keep in
-                    // 30 registers; an opaque copy of the base pins them to the step)
-                    unsigned fb = faddr[dx];
-                    asm volatile("" : "+v"(fb));
+                const unsigned char* sb = lds + RING_OFF + rd * WSTAGE + wfrag_off;
+                // (the per-fragment sums below are loop invariants the compiler would otherwise hoist out of the nine tap bodies and keep in
+                // 30 registers; an opaque copy of the base pins them to the step)
+                unsigned fb = faddr[dx];
+                asm volatile("" : "+v"(fb));
 #pragma unroll
-                    for (int i = 0; i < MF; ++i) {
-                        // (A/B, profiles/r04_mainloop_ab.txt: switching the SCALAR part of the address instead - a zero page as large as a fragment's
-                        // pixel range, one v_add per fragment - removes 2 v_readlane + 1 v_cndmask per fragment and step and measured 4-8 % SLOWER)
-                        unsigned a = fb + foff(i);
-                        if (HM == HM_CONV && dy != 1) {
-                            bool ok = (vmask >> (2 * i + (dy == 2 ? 1 : 0))) & 1u;
-                            if (W_ == 8) ok = ok || (upper_half != (dy == 2));      // (per lane: the other image line of the fragment has its neighbour inside the image)
-                            a = ok ? a : zfrag - (unsigned)(dy * LINE * 64);
-                        }
-                        xf[i] = *reinterpret_cast<const bf16x8*>(lds + a + dy * LINE * 64);
+                for (int i = 0; i < MF; ++i) {
+                    // (A/B, profiles/r04_mainloop_ab.txt: switching the SCALAR part of the address instead - a zero page as large as a fragment's
+                    // pixel range, one v_add per fragment - removes 2 v_readlane + 1 v_cndmask per fragment and step and measured 4-8 % SLOWER)
+                    unsigned a = fb + foff(i);
+                    if (HM == HM_CONV && dy != 1) {
+                        bool ok = (vmask >> (2 * i + (dy == 2 ? 1 : 0))) & 1u;
+                        a = ok ? a : zfrag - (unsigned)(dy * LINE * 64);
                     }
-#pragma unroll
-                    for (int j = 0; j < NF; ++j) wf[j] = *reinterpret_cast<const bf16x8*>(sb + j * 16 * ROWB);
+                    xf[i] = *reinterpret_cast<const bf16x8*>(lds + a + dy * LINE * 64);
                 }
+#pragma unroll
+                for (int j = 0; j < NF; ++j) wf[j] = *reinterpret_cast<const bf16x8*>(sb + j * 16 * ROWB);
                 // ---- loaders: the halo image LA chunks ahead (first step of a chunk), then the weights 3 steps ahead
                 if constexpr (tap == G::XF0 % NT) xf_begin();     // (ahead of this step's issue: with NT <= XF0 the chain belongs to the PREVIOUS issue)
                 if constexpr (tap == 0) issue_halo();
@@ -505,7 +467,7 @@ __global__ __launch_bounds__(512, 2) void conv_halo_kernel(GP p, int ntiles) {
                 // DMA ops younger than the pieces of the NEXT step's weight stage (issued two steps ago): two weight stages, plus the halo
                 // pieces + table piece when one of the last two issue points was a chunk's first step (they are issued AHEAD of that step's weights)
                 constexpr int HL = (tap == 0 || tap == 1) ? HPW + (XF ? 1 : 0) : 0;
-                if (grp == 1 && !CABL(32768)) {
+                if (grp == 1) {
                     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                     __builtin_amdgcn_sched_barrier(0);
                     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * 2 + HL) : "memory");
@@ -518,8 +480,8 @@ __global__ __launch_bounds__(512, 2) void conv_halo_kernel(GP p, int ntiles) {
                 constexpr int NOPS = HPW * 4 * 15, NSLOT = G::XFN * 30;
                 static_for<0, MF * NF>([&](auto n_) {
                     constexpr int n = decltype(n_)::value, i = n / NF, j = n % NF;
-                    if (!CABL(2)) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[j], xf[i], acc[i][j], 0, 0, 0);
-                    if constexpr (XF && XSTEP >= 0 && XSTEP < G::XFN && !CABL(16384)) {
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[j], xf[i], acc[i][j], 0, 0, 0);
+                    if constexpr (XF && XSTEP >= 0 && XSTEP < G::XFN) {
                         constexpr int s0 = XSTEP * 30 + n;
                         constexpr int o0 = (s0 * NOPS) / NSLOT, o1 = ((s0 + 1) * NOPS) / NSLOT;
                         static_for<o0, o1>([&](auto o) { xf_op(o); });
@@ -528,7 +490,7 @@ __global__ __launch_bounds__(512, 2) void conv_halo_kernel(GP p, int ntiles) {
                 });
                 __builtin_amdgcn_s_setprio(0);
                 __builtin_amdgcn_sched_barrier(0);
-                if (grp == 0 && !CABL(32768)) {
+                if (grp == 0) {
                     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // (its in-place ds_writes are inline asm)
                     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * 3 + HL) : "memory");
                     __builtin_amdgcn_s_barrier();
@@ -546,13 +508,6 @@ __global__ __launch_bounds__(512, 2) void conv_halo_kernel(GP p, int ntiles) {
         // Then (whole tile / owner) retire it (v3 epilogue: 16-row chunks through the wave's staging region)
         if constexpr (DONOR) {
             sk_publish<MF, NF>(p, acc, (int)blockIdx.x, wave, lane);
-        } else if (CABL(1)) {
-            float sum = 0.f;
-#pragma unroll
-            for (int i = 0; i < MF; ++i)
-#pragma unroll
-                for (int j = 0; j < NF; ++j) sum += acc[i][j][0] + acc[i][j][1] + acc[i][j][2] + acc[i][j][3];
-            if (sum == 123.456f) reinterpret_cast<float*>(p.out)[0] = sum;   // keeps the accumulators live
         } else {
             long long mw0;
             if (HM == HM_CONV) {
@@ -597,8 +552,8 @@ __global__ __launch_bounds__(512, 2) void conv_halo_kernel(GP p, int ntiles) {
             // staging reads of the epilogue (gemm_common.h e4_fragment RD): the temporal kernels take the lean asm form (one piece per LDS round trip: -6 %).  The 3 x 3
             // kernels keep the compiler-visible reads and their vmcnt(0) drains: once the in-place ds_write of the normalisation chain had freed their registers the
             // lean form fits all but the <W = 32, GroupNorm operand, no statistics> variant (tools/check_loop_scratch.py), but with 90-360 steps per tile the
-            // drains are not what their epilogue costs - -DCONV_3X3_READS=2 measured +-1 % on five launch classes and +6 % on one (profiles/r06_conv_w8_ab.txt)
-            e4_retire_tile<MF, NF, GN, (HM == HM_TEMP ? CONV_TEMP_READS : (W_ == 32 && XF && !GN ? 0 : CONV_3X3_READS))>(p, acc, nw0, lane_e, estage, rowfn, flushfn);
+            // drains are not what their epilogue costs - the lean form measured +-1 % on five launch classes and +6 % on one (profiles/r06_conv_w8_ab.txt)
+            e4_retire_tile<MF, NF, GN, (HM == HM_TEMP ? kConvTempReads : kConv3x3Reads)>(p, acc, nw0, lane_e, estage, rowfn, flushfn);
         }
 #pragma unroll
         for (int i = 0; i < MF; ++i)
@@ -631,12 +586,6 @@ int v3d_conv_halo_variant(const V3dGemmParams& p, int mode) {
         if (p.stride != 1 || p.upshift != 0 || p.pad_lo != 1 || p.Hin != p.Hout || p.Win != p.Wout) return 0;
         if (p.M % 192) return 0;
         const int W = p.Wout, H = p.Hout;
-        if (W == 8) {
-            // three whole 8 x 8 images per tile: no line of another image is ever needed; one statistics group per image
-            if (H != 8 || (p.gn_in && p.gn_in_rps != 64)) return 0;
-            if (p.gn_stats && p.gn_nslots < p.gn_rps / 96 + 2) return 0;
-            return 5;
-        }
         if (W != 64 && W != 32 && W != 16) return 0;
         if (H < 192 / W + 1) return 0;                              // a halo (tile rows + 2 lines) touches at most two images
         if (p.gn_in && p.gn_in_rps != (long long)H * W) return 0;   // one (scale, shift) row per image: the 2-D GroupNorm of the ResBlocks
@@ -677,7 +626,6 @@ int v3d_conv_halo_launch(const V3dGemmParams& p, int variant, void* stream) {
         case 2: return conv_halo_launch_t<HM_CONV, 32>(p, st);
         case 3: return conv_halo_launch_t<HM_CONV, 16>(p, st);
         case 4: return conv_halo_launch_t<HM_TEMP, 32>(p, st);
-        case 5: return conv_halo_launch_t<HM_CONV, 8>(p, st);
     }
     v3d_set_error("v3d_gemm(haloed): unknown variant %d", variant);
     return V3D_ERR_ARG;

@@ -15,35 +15,7 @@
 // work and the LDS-DMA issue of the next weights sit in the shadow of the MFMAs of the other two stages.  Both weight streams go
 // through double-buffered LDS slabs (buffer-load LDS-DMA, one barrier per tick); the weight stream is block-independent, so it
 // runs across row-block boundaries, where the last B of a block shares a tick with the first A of the next.
-#include <stdlib.h>
-
 #include "common.h"
-
-#ifndef FF_STAMPS
-#define FF_STAMPS 127   // which of the per-tick timeline stamps the DBG build takes (each costs a few hundred cycles)
-#endif
-#ifndef FF_BIAS_LDS
-#define FF_BIAS_LDS 0   // 1: b1 rides an exec-masked LDS-DMA piece with its W1 slab and is read from LDS in slots 8..15; 0: eight global
-                        // loads at the tick top (measured: 468 vs 500 us - the LDS variant lengthens stage B's slots by more than it saves)
-#endif
-#ifndef FF_GFRONT
-#define FF_GFRONT 6     // GELU pieces executed at the tick top, beside the bias loads
-#endif
-#ifndef FF_XBAR
-#define FF_XBAR 1   // 1: this tick's five W2 pieces may stay in flight across the barrier (vmcnt(5)): they are first read two ticks later,
-                    //    behind the next barrier; the first stage-B fragments of a tick are read AFTER the barrier.  0: vmcnt(0) and the
-                    //    next tick's first fragments prefetched before the barrier (their slab was complete one barrier earlier).
-                    //    Same box: 485 vs 518 us - the LDS-DMA stream is what the tick waits for, letting it run across the barrier wins.
-#endif
-#ifndef FF_AFIRST
-#define FF_AFIRST 0   // timing experiment: run stage A's MFMAs before stage B's inside a tick
-#endif
-#ifndef FF_BORDER
-#define FF_BORDER 0   // stage B MFMA order: 0 = k16 half outer (10 accumulators in turn, twice), 1 = accumulator outer (each twice in a row)
-#endif
-#ifndef FF_ABL
-#define FF_ABL 0   // timing experiments only (tools/ff_ablate.sh): 1 no GELU, 2 no DMA, 4 no LDS fragment reads in the slots, 8 no MFMA
-#endif
 
 namespace {
 
@@ -62,7 +34,6 @@ struct FFP {
     int hidden;
     float ln_eps;        // <LN> kernels: LayerNorm (no affine) of the input rows in registers before the first GEMM
     unsigned w1_bytes, w2_bytes;
-    int stagger_long, stagger_short, n_long;   // start delays (s_sleep units) spread over the CUs with one block more / less
 };
 
 template <int I, int N, typename F>
@@ -93,9 +64,7 @@ __device__ __forceinline__ void ff_tick_pipeline() {
 
 __device__ __forceinline__ int ff_swz(int row) { return (0x78 >> (((row >> 2) & 3) * 2)) & 3; }   // 64-byte LDS rows, see gemm.hip
 
-__device__ unsigned long long g_ff_dbg[4 * 16 * 8 + 4 * 4 * 8];   // [wave][tick 8..23][stamp] of block 0, then [wave][block 0..3][phase] (timeline build only)
-
-template <int C, bool DBG = false, bool LN = false>
+template <int C, bool LN>
 __global__ __launch_bounds__(256, 1) void ff_fused_kernel(FFP p) {
     constexpr int NT = C / 32;                 // 32-k LDS stages of a W1 slab
     constexpr int NK = C / 16;                 // k16 steps of stage A = resident x fragments
@@ -111,24 +80,9 @@ __global__ __launch_bounds__(256, 1) void ff_fused_kernel(FFP p) {
     static_assert(NO % 2 == 0, "staging geometry");
     constexpr int RING = 2 * W1_BYTES + 3 * W2_BYTES;   // W1 double-buffered, W2 three deep (see the tick description)
     constexpr int B2_OFF = RING + 4 * STAGE_REGION;   // b2 lives in LDS: the epilogue's only global loads are then its prefetches
-    constexpr int B1_OFF = B2_OFF + C * 4;             // b1 of the two W1 slabs in the ring (256 B each), see load of `bu / bv` below
-    constexpr int LDS_BYTES = B1_OFF + 2 * 256;
+    constexpr int LDS_BYTES = B2_OFF + C * 4;
     static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
     __shared__ __attribute__((aligned(1024))) unsigned char lds[LDS_BYTES];
-    unsigned long long* dbg = g_ff_dbg;   // timeline build: stamps go straight to global memory (no LDS left: 159.3 of 160 KiB are in use)
-    auto stamp = [&](int s_, int k) __attribute__((always_inline)) {
-        if (DBG && ((FF_STAMPS >> k) & 1) && blockIdx.x == 0 && s_ >= 8 && s_ < 24 && (threadIdx.x & 63) == 0) {
-            dbg[((threadIdx.x >> 6) * 16 + (s_ - 8)) * 8 + k] = __builtin_amdgcn_s_memtime();
-            // slot 7: the constant-rate counter (100 MHz) at the tick top - shader cycles per tick / real time per tick = the clock the CU holds (tools/clock_probe.py)
-            if (k == 0) dbg[((threadIdx.x >> 6) * 16 + (s_ - 8)) * 8 + 7] = __builtin_amdgcn_s_memrealtime();
-        }
-    };
-
-    int bcount = 0;
-    auto bstamp = [&](int k) __attribute__((always_inline)) {
-        if (DBG && blockIdx.x == 0 && bcount < 4 && (threadIdx.x & 63) == 0) dbg[512 + ((threadIdx.x >> 6) * 4 + bcount) * 8 + k] = __builtin_amdgcn_s_memtime();
-    };
-
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l31 = lane & 31, hi = lane >> 5;
@@ -139,13 +93,6 @@ __global__ __launch_bounds__(256, 1) void ff_fused_kernel(FFP p) {
     // ---- weight-slab loader: 1-KiB pieces (16 rows x 64 B) whose LDS image is: lane l -> row l >> 2, 16-byte chunk (l & 3) ^ swz(row)
     const bufrsrc_t rsW1 = make_rsrc(p.W1, p.w1_bytes);
     const bufrsrc_t rsW2 = make_rsrc(p.W2, p.w2_bytes);
-    const bufrsrc_t rsB1 = make_rsrc(p.b1, (unsigned)(2 * p.hidden * 4));
-    // b1 travels with its W1 slab: 64 floats per slab, one exec-masked DMA piece (16 lanes x 16 B) by wave 0.  A plain global load
-    // of it from inside a tick queues behind ~1500 cycles of LDS-DMA traffic in the CU's memory pipeline and stage A waited for it.
-    auto issue_b1 = [&](int par, int slab) __attribute__((always_inline)) {
-        if (wave == 0 && lane < 16)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsB1, (__attribute__((address_space(3))) void*)(lds + B1_OFF + par * 256), 16, lane * 16, slab * 256, 0, 0);
-    };
     // piece q = wave + 4 i of W1 is LDS stage i, rows 16 wave ..; of W2 rows 16 (wave + 4 i) ..: one base VGPR per stream, the rest is
     // a scalar offset (NOT the instruction's immediate: that one is added to the LDS address as well)
     // the packed weights are stored in DMA-piece order (packing.py ff_dma_tile_index: 16 rows x 64 B, LDS swizzle pre-applied), so a
@@ -185,32 +132,28 @@ __global__ __launch_bounds__(256, 1) void ff_fused_kernel(FFP p) {
     //   DMA:                 W1 slab ld1 -> w1ring[PD] (read next tick), W2 slab ld2 -> the W2 slot two ticks ahead of its use (D2)
     // A parity of -1 switches the stage off.  W2 is three slots deep: the slab DMA'd in tick j is first read in tick j + 2, so its
     // pieces (the last five a wave issues in a tick) may still be in flight at the tick's barrier - the wait there is vmcnt(5), and the
-    // LDS-DMA stream, which is what a tick ends up waiting for, never drains (FF_XBAR; the alternative use of the third slot,
-    // prefetching the next tick's first fragments ahead of the barrier, needs vmcnt(0) and measured 6 % slower).
+    // LDS-DMA stream, which is what a tick ends up waiting for, never drains (the alternative use of the third slot, prefetching the
+    // next tick's first fragments ahead of the barrier, needs vmcnt(0) and measured 6 % slower).
     constexpr int NPD = 4;             // LDS fragment reads run this many slots ahead of their MFMAs
     bf16x8 wf[NPD];                    // (carried across ticks: a tick prefetches the next one's first fragments)
     int w2_wr_slot = 0, w2_rd_slot = 0;
-    auto tick = [&](auto pa_c, auto pg_c, auto pb_c, auto pd_c, auto d2_c, auto nextb_c, int j) __attribute__((always_inline)) {
+    auto tick = [&](auto pa_c, auto pg_c, auto pb_c, auto pd_c, auto d2_c, int j) __attribute__((always_inline)) {
         constexpr int PA = decltype(pa_c)::value, PG = decltype(pg_c)::value, PB = decltype(pb_c)::value, PDM = decltype(pd_c)::value;
-        constexpr bool D2 = decltype(d2_c)::value != 0, NEXTB = decltype(nextb_c)::value != 0;
+        constexpr bool D2 = decltype(d2_c)::value != 0;
         constexpr int NB = PB >= 0 ? 2 * NO : 0, NA = PA >= 0 ? 4 * NT : 0, NS = 2 * NO + 4 * NT;
-        constexpr bool AF = FF_AFIRST && NB > 0 && NA > 0;
-        auto perm = [](int i) constexpr { return (FF_AFIRST && NB > 0 && NA > 0) ? (i < NA ? NB + i : i - NA) : i; };
-        stamp(j, 0);
-        // the slab accumulators start from b1 (row 8 g + 4 hi + c of fragment a <-> register 4 g + c), read from its LDS copy in slots
-        // 8..15 and moved into the accumulators in the four slots before stage A's first MFMA
+        // the slab accumulators start from b1 (row 8 g + 4 hi + c of fragment a <-> register 4 g + c): eight global loads at the tick
+        // top (issued inside the tick they queue behind ~1500 cycles of LDS-DMA traffic), moved into the accumulators in the four
+        // slots before stage A's first MFMA.  (b1 riding its W1 slab as an exec-masked
+        // LDS-DMA piece, read from LDS in slots 8..15, measured 500 against 468 us: it lengthens stage B's slots by more than it saves.)
         float4 bu[4], bv[4];
-        const unsigned char* bz = FF_BIAS_LDS ? lds + B1_OFF + (PA < 0 ? 0 : PA) * 256 + hi * 16
-                                              : reinterpret_cast<const unsigned char*>(p.b1 + (j == nslab ? 0 : j + 1) * 64 + hi * 4);
-        constexpr bool BIAS_TOP = PA >= 0 && (!FF_BIAS_LDS || NB < 16 || AF);   // all eight 16-byte pieces at the tick top
-        if constexpr (BIAS_TOP) {
+        const unsigned char* bz = reinterpret_cast<const unsigned char*>(p.b1 + (j == nslab ? 0 : j + 1) * 64 + hi * 4);
+        if constexpr (PA >= 0) {
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 bu[g] = *reinterpret_cast<const float4*>(bz + g * 32);
                 bv[g] = *reinterpret_cast<const float4*>(bz + 128 + g * 32);
             }
         }
-        const int b1_slab = ld1;
         int so1 = 0, so2 = 0, w2wr = 0;
         if constexpr (PDM >= 0) {
             so1 = ld1 * 64 * C * 2;
@@ -230,19 +173,18 @@ __global__ __launch_bounds__(256, 1) void ff_fused_kernel(FFP p) {
         auto rd = [&](auto fc) __attribute__((always_inline)) -> bf16x8 {
             constexpr int f = decltype(fc)::value;
             if constexpr (f < NB)
-                return *reinterpret_cast<const bf16x8*>(w2ring + (FF_BORDER ? f / 2 : f % NO) * 2048 + ((FF_BORDER ? f % 2 : f / NO) ? fb1 : fb0));
+                return *reinterpret_cast<const bf16x8*>(w2ring + (f % NO) * 2048 + ((f / NO) ? fb1 : fb0));
             else {
                 constexpr int q = f - NB;
                 return *reinterpret_cast<const bf16x8*>(w1ring + (PA < 0 ? 0 : PA) * W1_BYTES + (q >> 2) * W1_STAGE + (q & 1) * 2048 +
                                                         (((q >> 1) & 1) ? foff1 : foff0));
             }
         };
-        if constexpr (NB == 0 || AF || FF_XBAR) {   // no stage B: the first fragments are W1's, visible only after the barrier that just passed
-            ff_static_for<0, NPD>([&](auto fc) __attribute__((always_inline)) {
-                if constexpr (decltype(fc)::value < NB + NA) wf[decltype(fc)::value] = rd(std::integral_constant<int, perm(decltype(fc)::value)>{});
-            });
-        }
-        if constexpr (PA >= 0 && (NB < 16 || AF)) {   // no stage B to wait behind (first tick of a block): once per block, stall accepted
+        // the tick's first fragments, visible only after the barrier that just passed
+        ff_static_for<0, NPD>([&](auto fc) __attribute__((always_inline)) {
+            if constexpr (decltype(fc)::value < NB + NA) wf[decltype(fc)::value] = rd(fc);
+        });
+        if constexpr (PA >= 0 && NB < 16) {   // no stage B to wait behind (first tick of a block): once per block, stall accepted
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 sA[PA][0][4 * g] = bu[g].x; sA[PA][0][4 * g + 1] = bu[g].y; sA[PA][0][4 * g + 2] = bu[g].z; sA[PA][0][4 * g + 3] = bu[g].w;
@@ -250,9 +192,6 @@ __global__ __launch_bounds__(256, 1) void ff_fused_kernel(FFP p) {
             }
         }
         __builtin_amdgcn_sched_barrier(0);
-#ifndef FF_STAMP_B
-        stamp(j, 4);
-#endif
         float gx = 0.f, gz = 0.f, gq = 0.f, hprev = 0.f;
         u32x4 hw0 = {0, 0, 0, 0}, hw1 = {0, 0, 0, 0};
         auto gstep = [&](auto ms_c) __attribute__((always_inline)) {
@@ -280,51 +219,32 @@ __global__ __launch_bounds__(256, 1) void ff_fused_kernel(FFP p) {
                 }
             }
         };
-        constexpr int G_FRONT = FF_GFRONT;
-        if constexpr (PG >= 0 && (FF_ABL & 1) == 0) {
+        constexpr int G_FRONT = 6;     // GELU pieces executed at the tick top, beside the bias loads
+        if constexpr (PG >= 0) {
             ff_static_for<0, G_FRONT>([&](auto mc) __attribute__((always_inline)) { gstep(mc); });
             __builtin_amdgcn_sched_barrier(0);
         }
         ff_static_for<0, NS>([&](auto ic) __attribute__((always_inline)) {
             constexpr int i = decltype(ic)::value;
-            if constexpr (PA >= 0 && !BIAS_TOP && i >= 8 && i < 16) {
-                if constexpr (i & 1) bv[(i - 8) >> 1] = *reinterpret_cast<const float4*>(bz + 128 + ((i - 8) >> 1) * 32);
-                else bu[(i - 8) >> 1] = *reinterpret_cast<const float4*>(bz + ((i - 8) >> 1) * 32);
-            }
-            if constexpr (FF_BIAS_LDS && PDM >= 0 && i == 2) issue_b1(PDM, b1_slab);
-            if constexpr (PA >= 0 && NB >= 16 && !AF && i + 4 >= NB && i < NB) {
+            if constexpr (PA >= 0 && NB >= 16 && i + 4 >= NB && i < NB) {
                 constexpr int g = i + 4 - NB;
                 sA[PA][0][4 * g] = bu[g].x; sA[PA][0][4 * g + 1] = bu[g].y; sA[PA][0][4 * g + 2] = bu[g].z; sA[PA][0][4 * g + 3] = bu[g].w;
                 sA[PA][1][4 * g] = bv[g].x; sA[PA][1][4 * g + 1] = bv[g].y; sA[PA][1][4 * g + 2] = bv[g].z; sA[PA][1][4 * g + 3] = bv[g].w;
             }
             if constexpr (i < NB + NA) {
-                constexpr int pi = perm(i);
                 const bf16x8 w = wf[i % NPD];
-                if constexpr ((FF_ABL & 8) != 0) {
-                } else if constexpr (pi < NB && (FF_ABL & 64) != 0) {
-                } else if constexpr (pi < NB) {
-                    constexpr int bo = (FF_ABL & 16) ? (pi & 1) : (FF_BORDER ? pi / 2 : pi % NO), ba = FF_BORDER ? pi % 2 : pi / NO;
+                if constexpr (i < NB) {
+                    constexpr int bo = i % NO, ba = i / NO;
                     acc2[bo] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w, hh[PB < 0 ? 0 : PB][ba], acc2[bo], 0, 0, 0);
                 }
                 else {
-                    constexpr int q = pi - NB;
+                    constexpr int q = i - NB;
                     sA[PA < 0 ? 0 : PA][q & 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w, xr[q >> 1], sA[PA < 0 ? 0 : PA][q & 1], 0, 0, 0);
                 }
-                if constexpr (i + NPD < NB + NA && (FF_ABL & 4) == 0) wf[i % NPD] = rd(std::integral_constant<int, perm(i + NPD)>{});
+                if constexpr (i + NPD < NB + NA) wf[i % NPD] = rd(std::integral_constant<int, i + NPD>{});
             }
-#if !defined(FF_DMA_LATE)
-            if constexpr ((PDM >= 0 || D2) && i % 4 == 1 && (FF_ABL & 2) == 0) {
+            if constexpr ((PDM >= 0 || D2) && i % 4 == 1) {
                 constexpr int k = i / 4;
-#elif FF_DMA_LATE == 2
-            if constexpr ((PDM >= 0 || D2) && (FF_ABL & 2) == 0 && i >= 20 && i < 50 && i % 2 == 0) {
-                constexpr int k = (i - 20) / 2;
-#elif FF_DMA_LATE == 3
-            if constexpr ((PDM >= 0 || D2) && (FF_ABL & 2) == 0 && i >= 4 && i < 49 && i % 3 == 1) {
-                constexpr int k = (i - 4) / 3;
-#else
-            if constexpr ((PDM >= 0 || D2) && (FF_ABL & 2) == 0 && ((i >= 20 && i < 40 && i % 2 == 0) || (i >= 40 && i < 55 && (i - 40) % 3 == 0))) {
-                constexpr int k = i < 40 ? (i - 20) / 2 : PPW1 + (i - 40) / 3;
-#endif
                 if constexpr (k < PPW1 && PDM >= 0)
                     __builtin_amdgcn_raw_ptr_buffer_load_lds(rsW1, (__attribute__((address_space(3))) void*)(w1ring + PDM * W1_BYTES + k * W1_STAGE + wave * 1024),
                                                              16, (int)voff1, so1 + k * 4096, 0, 0);
@@ -337,45 +257,22 @@ __global__ __launch_bounds__(256, 1) void ff_fused_kernel(FFP p) {
             //   gelu(x) = relu(x) - |x| 2^-(z Q(z) + 1),  z = min(|x| / sqrt2, 4),  0.5 erfc(z) = 2^-(z Q(z) + 1)
             // Q: degree-3 fit of -log2(erfc(z)) / z weighted for the GELU error (|error| <= 8.6e-6 in fp32 Horner; the value is rounded
             // to bf16, 4e-3 relative, right after).  11 VALU + 1 transcendental per value.
-            // the 48 GELU pieces: G_FRONT of them at the tick top (0 now: the tick's first fragments are prefetched, nothing to wait for
-            // there), the rest spread evenly over the slots
-            if constexpr (PG >= 0 && (FF_ABL & 1) == 0) {
+            // the 48 GELU pieces: G_FRONT of them at the tick top, the rest spread evenly over the slots
+            if constexpr (PG >= 0) {
                 constexpr int NSTEP = 48 - G_FRONT;
-                if constexpr ((i == 0 || (NSTEP * i) / NS != (NSTEP * (i - 1)) / NS) && !((FF_ABL & 128) != 0 && i < 20)) gstep(std::integral_constant<int, G_FRONT + (NSTEP * i) / NS>{});
+                if constexpr (i == 0 || (NSTEP * i) / NS != (NSTEP * (i - 1)) / NS) gstep(std::integral_constant<int, G_FRONT + (NSTEP * i) / NS>{});
             }
             __builtin_amdgcn_sched_barrier(0);
-#ifdef FF_STAMP_B
-            if constexpr (i >= FF_STAMP_B && i < FF_STAMP_B + 7) stamp(j, 1 + i - FF_STAMP_B);
-#else
-            if constexpr (i == 19) stamp(j, 5);
-            if constexpr (i == 39) stamp(j, 6);
-#endif
         });
         if constexpr (PG >= 0) {
             hh[PG][0] = __builtin_bit_cast(bf16x8, hw0);
             hh[PG][1] = __builtin_bit_cast(bf16x8, hw1);
         }
-        if constexpr (NEXTB && !FF_AFIRST && !FF_XBAR) {     // next tick's first stage-B fragments: their W2 slab became visible at the previous barrier
-            const int nb0 = foff0 + w2_rd_slot * W2_BYTES, nb1 = foff1 + w2_rd_slot * W2_BYTES;
-            ff_static_for<0, NPD>([&](auto fc) __attribute__((always_inline)) {
-                constexpr int f = decltype(fc)::value;
-                wf[f] = *reinterpret_cast<const bf16x8*>(w2ring + (FF_BORDER ? f / 2 : f) * 2048 + ((FF_BORDER && (f % 2)) ? nb1 : nb0));
-            });
-        }
-#ifndef FF_STAMP_B
-        stamp(j, 1);
-#endif
-        // this wave's share of the next weights (and x / residual prefetches) has landed.  vmcnt(0), not vmcnt(5): the W2 pieces of
-        // this tick are read by the NEXT tick's pre-barrier prefetch, so the barrier below is the last one in front of their first use
-        if constexpr (FF_XBAR && D2) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
+        // this wave's share of the next weights (and x / residual prefetches) has landed, but for this tick's five W2 pieces: they are
+        // first read two ticks later, behind the next barrier
+        if constexpr (D2) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#ifndef FF_STAMP_B
-        stamp(j, 2);
-#endif
         __builtin_amdgcn_s_barrier();                      // ... everyone's has, and every LDS read of this tick was consumed
-#ifndef FF_STAMP_B
-        stamp(j, 3);
-#endif
     };
     using I0 = std::integral_constant<int, 0>;
     using I1 = std::integral_constant<int, 1>;
@@ -384,24 +281,12 @@ __global__ __launch_bounds__(256, 1) void ff_fused_kernel(FFP p) {
     // ---- prologue: W1(0), W1(1), W2(0) in flight (as the ticks before a block would have left them), first x block, A(0) alone
     long long blk = blockIdx.x;
     if (tid < C / 4) reinterpret_cast<float4*>(lds + B2_OFF)[tid] = reinterpret_cast<const float4*>(p.b2)[tid];
-    {   // All CUs run identical blocks, so without this they stay in lockstep and their epilogues (and x fetches) hit HBM as one
-        // burst of grid x 240 KB while the memory system idles during the ticks.  The CUs that get one block less have a whole block
-        // time of slack; the others are spread over a quarter of it.
-        const int c = (int)blockIdx.x;
-        const int n = c < p.n_long ? (p.n_long > 1 ? c * p.stagger_long / p.n_long : 0)
-                                   : ((int)gridDim.x > p.n_long ? (c - p.n_long) * p.stagger_short / ((int)gridDim.x - p.n_long) : 0);
-        for (int i = 0; i < n; ++i) __builtin_amdgcn_s_sleep(64);
-    }
     ff_static_for<0, 2 * PPW1>([&](auto ic) __attribute__((always_inline)) {
         constexpr int k = decltype(ic)::value % PPW1, par = decltype(ic)::value / PPW1;
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rsW1, (__attribute__((address_space(3))) void*)(w1ring + par * W1_BYTES + k * W1_STAGE + wave * 1024), 16,
                                                  (int)voff1, par * 64 * C * 2 + k * 4096, 0, 0);
     });
     ld1 = 2;
-    if (FF_BIAS_LDS) {
-        issue_b1(0, 0);
-        issue_b1(1, 1);
-    }
     ff_static_for<0, PPW2>([&](auto ic) __attribute__((always_inline)) {
         constexpr int k = decltype(ic)::value;
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rsW2, (__attribute__((address_space(3))) void*)(w2ring + (wave + 4 * k) * 1024), 16, (int)voff2,
@@ -413,7 +298,7 @@ __global__ __launch_bounds__(256, 1) void ff_fused_kernel(FFP p) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     if constexpr (LN) ln_rows_inplace<NK>(xr, p.ln_eps);
     __builtin_amdgcn_s_barrier();
-    tick(I0{}, IX{}, IX{}, IX{}, I0{}, I0{}, -1);
+    tick(I0{}, IX{}, IX{}, IX{}, I0{}, -1);
 
     // residual rows of one epilogue pass (64 channels): res1 coalesced (row c >> 3, 16-byte chunk c & 7), res2 in the MFMA layout
     u32x4 r1[2][4];
@@ -444,24 +329,19 @@ __global__ __launch_bounds__(256, 1) void ff_fused_kernel(FFP p) {
 
     while (true) {
         const long long mw0 = blk * 128 + wave * 32;
-        bstamp(0);
-        tick(I1{}, I0{}, IX{}, I0{}, I1{}, I1{}, 0);       // A(1) G(0)            DMA W1(2) W2(1)
-        bstamp(1);
+        tick(I1{}, I0{}, IX{}, I0{}, I1{}, 0);       // A(1) G(0)            DMA W1(2) W2(1)
         for (int j = 1; j + 2 < nslab; j += 2) {
-            tick(I0{}, I1{}, I0{}, I1{}, I1{}, I1{}, j);   // A(j+1) G(j) B(j-1)   DMA W1(j+2) W2(j+1)
-            tick(I1{}, I0{}, I1{}, I0{}, I1{}, I1{}, j + 1);
+            tick(I0{}, I1{}, I0{}, I1{}, I1{}, j);   // A(j+1) G(j) B(j-1)   DMA W1(j+2) W2(j+1)
+            tick(I1{}, I0{}, I1{}, I0{}, I1{}, j + 1);
         }
         // penultimate tick: no A (its x fragments are dead: fetch the next block's), then the boundary tick A'(0) + B(last)
         const long long nxt = blk + gridDim.x;
-        bstamp(2);
         load_x(nxt < nblocks ? nxt : blk);
-        tick(IX{}, I1{}, I0{}, I1{}, I0{}, I1{}, nslab - 1);   // G(last) B(last-1)    DMA W1'(1)
+        tick(IX{}, I1{}, I0{}, I1{}, I0{}, nslab - 1);   // G(last) B(last-1)    DMA W1'(1)
         // <LN>: the block's LayerNorm on the freshly loaded rows (their load latency went under the tick above); ~170 VALU per block
         if constexpr (LN) ln_rows_inplace<NK>(xr, p.ln_eps);
-        bstamp(3);
         fetch_res(mw0, 0, r1[0], r2[0]);                   // the epilogue's first pass: in flight under the boundary tick
-        tick(I0{}, IX{}, I1{}, IX{}, I1{}, I0{}, nslab);   // A'(0) B(last)        DMA W2'(0)
-        bstamp(4);
+        tick(I0{}, IX{}, I1{}, IX{}, I1{}, nslab);   // A'(0) B(last)        DMA W2'(0)
 
         // ---- block epilogue: out = c_acc (acc + b2) + c1 res1 + c2 res2, 32 rows x 64 channels per staging pass
         {
@@ -520,8 +400,6 @@ __global__ __launch_bounds__(256, 1) void ff_fused_kernel(FFP p) {
                 }
             }
         }
-        bstamp(5);
-        ++bcount;
         if (nxt >= nblocks) break;
         blk = nxt;
     }
@@ -529,10 +407,6 @@ __global__ __launch_bounds__(256, 1) void ff_fused_kernel(FFP p) {
 }
 
 }  // namespace
-
-extern "C" int v3d_debug_ff_timeline(unsigned long long* host_out) {
-    return hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_ff_dbg), sizeof(g_ff_dbg)) == hipSuccess ? 0 : -1;
-}
 
 static int ff_fused_launch(const void* x, int64_t ldx, float ln_eps, const void* W1p, const float* b1, const void* W2p, const float* b2,
                            const void* res1, int64_t ldr1, const void* res2, int64_t ldr2, const float* coef, int64_t coef_rpg,
@@ -556,27 +430,10 @@ static int ff_fused_launch(const void* x, int64_t ldx, float ln_eps, const void*
     p.w2_bytes = (unsigned)((long long)C * hidden * 2);
     const long long nblocks = M / 128;
     const int grid = (int)(nblocks < v3d_num_cus() ? nblocks : v3d_num_cus());
-    static int dbg = -1, stagger = 0;   // V3D_FF_STAGGER: one block time in s_sleep(64) units (~4096 cycles each), e.g. 36; off by
-                                        // default (measured neutral once the epilogue prefetched its residuals: 494.5 vs 493.7 us)
-    if (dbg < 0) {
-        const char* e = getenv("V3D_FF_TIMELINE");
-        dbg = e ? atoi(e) : 0;
-        if (const char* s2 = getenv("V3D_FF_STAGGER")) stagger = atoi(s2);
-    }
-    p.n_long = 0; p.stagger_long = 0; p.stagger_short = 0;
-    if (nblocks > grid && stagger > 0) {
-        const int rem = (int)(nblocks % grid);
-        p.n_long = rem ? rem : grid;
-        p.stagger_long = stagger / 4;
-        p.stagger_short = rem ? stagger * hidden / 1280 : 0;
-        p.stagger_long = p.stagger_long * hidden / 1280;
-    }
     if (ln_eps > 0.f)
-        hipLaunchKernelGGL((ff_fused_kernel<320, false, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, p);
-    else if (dbg)
         hipLaunchKernelGGL((ff_fused_kernel<320, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, p);
     else
-        hipLaunchKernelGGL((ff_fused_kernel<320>), dim3(grid), dim3(256), 0, (hipStream_t)stream, p);
+        hipLaunchKernelGGL((ff_fused_kernel<320, false>), dim3(grid), dim3(256), 0, (hipStream_t)stream, p);
     return v3d_check_launch("v3d_ff_fused");
 }
 

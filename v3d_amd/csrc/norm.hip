@@ -1,6 +1,5 @@
 // GroupNorm (stats / apply), LayerNorm and row softmax for channels-last bf16 activations (gfx950).
 // All of these are HBM-bound: every access is a 16-byte (8 x bf16) per-lane vector, coalesced along channels.
-#include <stdlib.h>
 
 #include "common.h"
 
@@ -484,15 +483,10 @@ int gn_stats_launch(const char* who, const void* x1, int64_t C1, const void* x2,
                 (long long)nslots, (long long)imgs_per_stat);
     const GNGeom g = gn_geom(C1 + C2);
     long long chunks, rpb;
-    static long long target = -1;
-    if (target < 0) {
-        const char* e = getenv("V3D_GN_BLOCKS");   // tuning knob (tools/gn_bench.py)
-        target = e ? atoll(e) : 0;
-    }
     // few, long blocks (rounds 1-2: every block ended in 64 global atomics; now one 8-byte store per group, but ~1 block per CU still
     // reads at the HBM rate); very large inputs (VAE, > 256 MB) want ~3 blocks per CU to keep HBM busy
     const long long bytes = n_img * S * (C1 + C2) * 2;
-    gn_grid(n_img, S, g, chunks, rpb, target > 0 ? target : (bytes > (256ll << 20) ? 768 : 256));
+    gn_grid(n_img, S, g, chunks, rpb, bytes > (256ll << 20) ? 768 : 256);
     if (chunks * imgs_per_stat > nslots) {       // every block of a statistics group needs its own slot
         chunks = nslots / imgs_per_stat;
         rpb = (S + chunks - 1) / chunks;
@@ -679,15 +673,10 @@ static int gn_small_groups(long long rows, long long C1, long long C2, int group
     if (groups != 32 || C % 32 || C1 % 8 || rows <= 0) return 0;
     const long long cpg = C / 32;
     if (cpg % 8) return 0;                                        // a 16-byte vector must lie inside one channel group
-    static int gb_max = -1;
-    if (gb_max < 0) {
-        const char* e = getenv("V3D_GN_SMALL_GB");                // tuning knob (tools/gn_small_bench.py): largest channel-group count per block
-        gb_max = e ? atoi(e) : 1;      // round 5 (profiles/r05_gn_small_gb.txt): the smallest slice with >= 64-byte row segments wins or ties everywhere
-                                       // (16 x 16 transformer norm 29.6 -> 20.0 us, two-source 8 x 8 norm 17.8 -> 12.5 us): more, shorter blocks
-        if (gb_max < 1) gb_max = 1;
-    }
+    // the smallest slice with >= 64-byte row segments wins or ties everywhere (profiles/r05_gn_small_gb.txt: 16 x 16 transformer norm
+    // 29.6 -> 20.0 us, two-source 8 x 8 norm 17.8 -> 12.5 us): more, shorter blocks
     for (int gb = 8; gb >= 1; gb >>= 1) {
-        if (gb > gb_max && gb > 1 && (gb / 2) * cpg * 2 >= 64) continue;      // (a smaller slice still has row segments >= 64 bytes)
+        if (gb > 1 && (gb / 2) * cpg * 2 >= 64) continue;         // (a smaller slice still has row segments >= 64 bytes)
         if (C1 % (gb * cpg) && C2) continue;                      // a block's slice must lie inside one source
         if (rows * (gb * cpg / 8) <= 256 * 24 && gb * cpg * 2 >= 64) return gb;
     }

@@ -14,8 +14,6 @@
 //     fragments with the MFMA operands swapped, so a lane ends up with 4 consecutive tokens of one channel: no transpose anywhere.
 // The token tensor is read once and no normalised copy is ever written.  The weight stream is block-independent and runs across
 // row-block boundaries; the next block's rows are fetched while the current block computes.
-#include <stdlib.h>
-
 #include <type_traits>
 
 #include "common.h"
@@ -48,27 +46,24 @@ __device__ __forceinline__ void pj_static_for(F&& f) {
 
 __device__ __forceinline__ int pj_swz(int row) { return (0x78 >> (((row >> 2) & 3) * 2)) & 3; }   // 64-byte LDS rows, see gemm.hip
 
-__device__ unsigned long long g_pj_dbg[8 * 32 * 8];   // timeline build (V3D_LNPROJ_TIMELINE=1): [wave][stream slab 16..47][stamp]
-
-// NW waves of RF x 32 rows share every weight slab (block = NW * RF * 32 rows):
-//   <8, 1>  two waves per SIMD, 32 rows each;   <4, 2>  one wave per SIMD, 64 rows each (every weight fragment read from LDS feeds two MFMAs:
-//   at 32 rows per wave the fragment reads alone need the whole LDS port, 1 KiB per 32-cycle MFMA per SIMD);   <4, 1>  128-row blocks for
-//   shapes the other two do not divide.
-// One iteration of the slab loop = the 40 * RF MFMAs of slab j in 10 fenced steps of 2 k-steps, with the PREVIOUS slab's output path slotted
-// between them: its tile was rounded to bf16 (bias added) into 16 * RF registers at the top of the iteration, ahead of the barrier; steps 0-4
+// NW waves of 32 rows share every weight slab (block = NW * 32 rows): <8> two waves per SIMD, 256-row blocks;  <4> 128-row blocks for
+// shapes that 256 does not divide.  (One wave per SIMD with 64 rows each, every weight fragment read from LDS feeding two MFMAs, measured
+// 161 against 148 us at level 0.)
+// One iteration of the slab loop = the 40 MFMAs of slab j in 10 fenced steps of 2 k-steps, with the PREVIOUS slab's output path slotted
+// between them: its tile was rounded to bf16 (bias added) into 16 registers at the top of the iteration, ahead of the barrier; steps 0-4
 // carry the LDS-DMA pieces of slab j + 2 and the staging writes, steps 5-7 the staging reads and the 16-byte-per-lane global stores.  (The
 // first version ran "multiply, then stage, then store" per slab with all waves in the same phase: 5900 cycles per slab for 2560 of MFMA.)
-template <int C, int NW, int RF, bool DBG = false>
+template <int C, int NW>
 __global__ __launch_bounds__(64 * NW, NW / 4) void ln_proj_kernel(PP p) {
-    constexpr int NK = C / 16;                  // k16 steps = resident row fragments per 32 rows
+    constexpr int NK = C / 16;                  // k16 steps = resident row fragments
     constexpr int NT = C / 32;                  // 32-k LDS stages of a slab
     constexpr int SLAB = 64 * C * 2;            // 64 weight rows
     constexpr int PPW = NT * 4 / NW;            // 1-KiB pieces per wave per slab
-    constexpr int RW = 32 * RF;                 // rows per wave
+    constexpr int RW = 32;                      // rows per wave
     constexpr int BR = RW * NW;                 // rows per block
     constexpr int NSTEP = NK / 4 * 2;           // fenced steps of 2 k-steps
     constexpr int NST = RW / 8;                 // 1-KiB store instructions per wave per slab
-    constexpr int NP = RF * 8;                  // (row fragment, channel half, g) register pairs of a tile
+    constexpr int NP = 8;                       // (channel half, g) register pairs of a tile
     static_assert(PPW * NW == NT * 4 && PPW % 5 == 0 && NK % 4 == 0 && NSTEP == 10, "schedule below is written for C = 320");
     constexpr int NSLOT = 3;
     constexpr int ST_BYTES = RW * 144;          // per-wave output staging: RW rows x (128 + 16) B row-major; 64 channel rows x RW tokens (swizzled) transposed
@@ -84,7 +79,6 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void ln_proj_kernel(PP p) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l31 = lane & 31, hi = lane >> 5;
-    const long long nblocks = p.M / BR;
     const int nslab = p.N / 64;
     const int nrm_slabs = p.n_rm / 64;
     float* gsm = reinterpret_cast<float*>(lds + GB_OFF);
@@ -102,7 +96,6 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void ln_proj_kernel(PP p) {
     const int ts0 = has_tail ? tpart * nslab / p.parts : 0, ts1 = has_tail ? (tpart + 1) * nslab / p.parts : 0;      // the tail item's slabs [ts0, ts1)
     const long long tail_blk = (long long)p.full * gridDim.x + (has_tail ? bid / p.parts : 0);
     const long long total = (long long)p.full * nslab + (ts1 - ts0);
-    (void)nblocks;
     int ld_slab = p.full > 0 ? 0 : ts0, ld_slot = 0, ld_full_left = p.full;
     bool ld_live = true;
     auto issue_piece = [&](int i) __attribute__((always_inline)) {      // piece i of this wave's PPW pieces of the slab being loaded
@@ -124,26 +117,18 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void ln_proj_kernel(PP p) {
     const int foff0 = l31 * 64 + (((0 + hi) ^ pj_swz(l31)) * 16);
     const int foff1 = l31 * 64 + (((2 + hi) ^ pj_swz(l31)) * 16);
 
-    bf16x8 xr[RF][NK];
+    bf16x8 xr[NK];
     auto load_rows = [&](long long blk) __attribute__((always_inline)) {
+        const bf16_t* xz = p.x + (blk * BR + wave * RW + l31) * p.ldx + hi * 8;
 #pragma unroll
-        for (int r = 0; r < RF; ++r) {
-            const bf16_t* xz = p.x + (blk * BR + wave * RW + r * 32 + l31) * p.ldx + hi * 8;
-#pragma unroll
-            for (int k = 0; k < NK; ++k) xr[r][k] = *reinterpret_cast<const bf16x8*>(xz + k * 16);
-        }
-    };
-    // LayerNorm of the wave's rows in place (common.h ln_rows_inplace: dot2 statistics, gamma / beta folded into the weights / the output bias)
-    auto normalise = [&]() __attribute__((always_inline)) {
-#pragma unroll
-        for (int r = 0; r < RF; ++r) ln_rows_inplace<NK>(xr[r], p.eps);
+        for (int k = 0; k < NK; ++k) xr[k] = *reinterpret_cast<const bf16x8*>(xz + k * 16);
     };
 
     // ---- output path of one slab tile, cut into the pieces the slab loop slots between its MFMAs
-    //   row-major (TRE = 0): acc[r][t][4 g + c] = out[token row0 + 32 r + l31][channel 64 sl + 32 t + 8 g + 4 hi + c]
-    //   transposed (TRE = 1): acc[r][t][4 g + c] = outT[image][channel 64 (sl - nrm_slabs) + 32 t + l31][token pix0 + 32 r + 8 g + 4 hi + c]
-    f32x16 acc[RF][2];
-    u32x2 pk[RF][2][4];
+    //   row-major (TRE = 0): acc[t][4 g + c] = out[token row0 + l31][channel 64 sl + 32 t + 8 g + 4 hi + c]
+    //   transposed (TRE = 1): acc[t][4 g + c] = outT[image][channel 64 (sl - nrm_slabs) + 32 t + l31][token pix0 + 8 g + 4 hi + c]
+    f32x16 acc[2];
+    u32x2 pk[2][4];
     u32x4 sr[NST];
     long long p_row0 = 0, p_img = 0, p_pix0 = 0;    // the tile in pk / staging: its rows and slab
     int p_sl = 0;
@@ -156,32 +141,28 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void ln_proj_kernel(PP p) {
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
                     const f32x4 bb = *reinterpret_cast<const f32x4*>(gsm + p_sl * 64 + t * 32 + 8 * g + 4 * hi);
-#pragma unroll
-                    for (int r = 0; r < RF; ++r)
-                        pk[r][t][g] = u32x2{pack2bf(acc[r][t][4 * g + 0] + bb[0], acc[r][t][4 * g + 1] + bb[1]),
-                                            pack2bf(acc[r][t][4 * g + 2] + bb[2], acc[r][t][4 * g + 3] + bb[3])};
+                    pk[t][g] = u32x2{pack2bf(acc[t][4 * g + 0] + bb[0], acc[t][4 * g + 1] + bb[1]),
+                                     pack2bf(acc[t][4 * g + 2] + bb[2], acc[t][4 * g + 3] + bb[3])};
                 }
             } else {
                 const float bb = gsm[p_sl * 64 + t * 32 + l31];
 #pragma unroll
-                for (int r = 0; r < RF; ++r)
-#pragma unroll
-                    for (int g = 0; g < 4; ++g)
-                        pk[r][t][g] = u32x2{pack2bf(acc[r][t][4 * g + 0] + bb, acc[r][t][4 * g + 1] + bb),
-                                            pack2bf(acc[r][t][4 * g + 2] + bb, acc[r][t][4 * g + 3] + bb)};
+                for (int g = 0; g < 4; ++g)
+                    pk[t][g] = u32x2{pack2bf(acc[t][4 * g + 0] + bb, acc[t][4 * g + 1] + bb),
+                                     pack2bf(acc[t][4 * g + 2] + bb, acc[t][4 * g + 3] + bb)};
             }
         }
     };
-    auto stage_write = [&](auto tre_, auto i_) __attribute__((always_inline)) {       // pair i = (r, t, g)
+    auto stage_write = [&](auto tre_, auto i_) __attribute__((always_inline)) {       // pair i = (t, g)
         constexpr bool TRE = decltype(tre_)::value;
-        constexpr int i = decltype(i_)::value, r = i / 8, t = (i / 4) & 1, g = i & 3;
+        constexpr int i = decltype(i_)::value, t = i / 4, g = i & 3;
         if constexpr (!TRE) {
             const unsigned a = stg_a + l31 * 144 + hi * 8;
-            asm volatile("ds_write_b64 %0, %1 offset:%2" ::"v"(a), "v"(pk[r][t][g]), "n"(r * 32 * 144 + (t * 32 + 8 * g) * 2) : "memory");
+            asm volatile("ds_write_b64 %0, %1 offset:%2" ::"v"(a), "v"(pk[t][g]), "n"((t * 32 + 8 * g) * 2) : "memory");
         } else {
             const int row = t * 32 + l31;
-            const unsigned a = stg_a + row * RB + (((r * 4 + g) ^ tswz(row)) * 16) + hi * 8;
-            asm volatile("ds_write_b64 %0, %1" ::"v"(a), "v"(pk[r][t][g]) : "memory");
+            const unsigned a = stg_a + row * RB + ((g ^ tswz(row)) * 16) + hi * 8;
+            asm volatile("ds_write_b64 %0, %1" ::"v"(a), "v"(pk[t][g]) : "memory");
         }
     };
     auto stage_read = [&](auto tre_, auto i_) __attribute__((always_inline)) {
@@ -215,16 +196,11 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void ln_proj_kernel(PP p) {
     issue_all();
     issue_all();
 #pragma unroll
-    for (int r = 0; r < RF; ++r)
+    for (int t = 0; t < 2; ++t)
 #pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[r][t][e] = 0.f;
+        for (int e = 0; e < 16; ++e) acc[t][e] = 0.f;
 
     long long j = 0;                       // weight-stream index of the slab about to be consumed
-    auto stamp = [&](int k) __attribute__((always_inline)) {
-        if (DBG && blockIdx.x == 0 && j >= 16 && j < 48 && lane == 0) g_pj_dbg[(wave * 32 + (int)(j - 16)) * 8 + k] = __builtin_amdgcn_s_memtime();
-    };
     int rd_slot = 0, sl = p.full > 0 ? 0 : ts0, sl0 = sl, sl_end = p.full > 0 ? nslab : ts1, full_left = p.full;
     long long blk = p.full > 0 ? (long long)blockIdx.x : tail_blk, row0 = 0, img = 0, pix0 = 0;
 
@@ -233,21 +209,16 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void ln_proj_kernel(PP p) {
         constexpr bool TRM = decltype(trm_)::value;
         pack_tile(tre_);
 #pragma unroll
-        for (int r = 0; r < RF; ++r)
+        for (int t = 0; t < 2; ++t)
 #pragma unroll
-            for (int t = 0; t < 2; ++t)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) acc[r][t][e] = 0.f;
+            for (int e = 0; e < 16; ++e) acc[t][e] = 0.f;
         // this wave's pieces of slab j have landed when only the ops issued after them are outstanding: the stores of tile j - 3 (issued
         // after the pieces in iteration j - 2), and iteration j - 1's pieces and stores.  Around a block boundary (row loads in the queue,
         // no stores in the very first iteration) drain instead.
-        stamp(0);
         if (j < 3 || sl - sl0 < 2) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PPW + 2 * NST) : "memory");
-        stamp(1);
         __builtin_amdgcn_s_barrier();          // everyone's pieces landed; everyone finished reading the slot refilled below
         asm volatile("" ::: "memory");
-        stamp(2);
         ld_live = j + 2 < total;               // stream tail: dummy pieces keep the per-iteration op count constant for the counted waits
         const unsigned char* sb = lds + rd_slot * SLAB;
         rd_slot = (rd_slot + 1 == NSLOT) ? 0 : rd_slot + 1;
@@ -267,16 +238,13 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void ln_proj_kernel(PP p) {
             if constexpr (s + 1 < NSTEP) load_frags(std::integral_constant<int, s + 1>{});
             pj_static_for<0, 2>([&](auto q_) {
                 constexpr int q = decltype(q_)::value;
-                pj_static_for<0, RF>([&](auto r_) {
-                    constexpr int r = decltype(r_)::value;
-                    if constexpr (!TRM) {
-                        acc[r][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[s & 1][q][0], xr[r][2 * s + q], acc[r][0], 0, 0, 0);
-                        acc[r][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[s & 1][q][1], xr[r][2 * s + q], acc[r][1], 0, 0, 0);
-                    } else {
-                        acc[r][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xr[r][2 * s + q], wf[s & 1][q][0], acc[r][0], 0, 0, 0);
-                        acc[r][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xr[r][2 * s + q], wf[s & 1][q][1], acc[r][1], 0, 0, 0);
-                    }
-                });
+                if constexpr (!TRM) {
+                    acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[s & 1][q][0], xr[2 * s + q], acc[0], 0, 0, 0);
+                    acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[s & 1][q][1], xr[2 * s + q], acc[1], 0, 0, 0);
+                } else {
+                    acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xr[2 * s + q], wf[s & 1][q][0], acc[0], 0, 0, 0);
+                    acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xr[2 * s + q], wf[s & 1][q][1], acc[1], 0, 0, 0);
+                }
             });
             if constexpr (s < 5) {
                 pj_static_for<s * (PPW / 5), (s + 1) * (PPW / 5)>([&](auto i_) { issue_piece(decltype(i_)::value); });
@@ -292,14 +260,14 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void ln_proj_kernel(PP p) {
             __builtin_amdgcn_sched_barrier(0);
         });
         advance_load();
-        stamp(3);
     };
 
     // (rows are loaded AND normalised in one place, so that no row load is pending on the loop back edge: with the normalisation at the top
     //  of the next iteration the compiler kept vmcnt(10..20) waits in front of the MFMAs of every step, which drain the weight stream)
     auto begin_block = [&]() __attribute__((always_inline)) {
         load_rows(blk);
-        normalise();
+        // LayerNorm of the wave's rows in place (common.h ln_rows_inplace: dot2 statistics, gamma / beta folded into the weights / the output bias)
+        ln_rows_inplace<NK>(xr, p.eps);
         row0 = blk * BR + wave * RW;
         img = row0 / p.S;
         pix0 = row0 - img * p.S;
@@ -346,11 +314,6 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void ln_proj_kernel(PP p) {
 
 }  // namespace
 
-// experiments only (not part of the ABI header): copy the slab timeline of the instrumented build out
-extern "C" int v3d_debug_lnproj_timeline(unsigned long long* host_out) {
-    return hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_pj_dbg), sizeof(g_pj_dbg)) == hipSuccess ? 0 : -1;
-}
-
 extern "C" int v3d_ln_proj(const void* x, int64_t ldx, float eps, const void* Wp, const float* bias, void* out, int64_t ldo, void* outT,
                            int64_t M, int32_t C, int32_t N, int32_t n_rm, int64_t S, v3d_stream_t stream) {
     V3D_REQUIRE(x && Wp, "v3d_ln_proj: null pointer");
@@ -368,37 +331,27 @@ extern "C" int v3d_ln_proj(const void* x, int64_t ldx, float eps, const void* Wp
     p.N = N; p.n_rm = n_rm; p.Ct = N - n_rm;
     p.w_bytes = (unsigned)((size_t)N * C * 2);
     p.eps = eps;
-    static int tl = -1, cfg = -1;
-    if (tl < 0) { const char* e = getenv("V3D_LNPROJ_TIMELINE"); tl = e ? atoi(e) : 0; }
-    if (cfg < 0) { const char* e = getenv("V3D_LNPROJ_CFG"); cfg = e ? atoi(e) : 1; }     // A/B knob: 0 = <4 waves, 64 rows> (161 us at level 0), 1 = <8, 32> (148 us, default), 2 = <4, 32> (164 us)
-    const bool big = cfg != 2 && M % 256 == 0 && (n_rm == N || S % 256 == 0);
+    const bool big = M % 256 == 0 && (n_rm == N || S % 256 == 0);
     const long long nblocks = M / (big ? 256 : 128);
     const int cus = v3d_num_cus();
     // work list: whole rounds of row blocks, then the remaining R row blocks cut into `parts` slab ranges each so that the last round is (nearly) as
     // wide as the chip: M = 147456 at 256 rows = 576 row blocks = 2 rounds + 64 -> 4 parts of 3-4 of the 15 slabs instead of a third round a quarter
-    // full.  V3D_LNPROJ_SPLIT=0: the classic assignment (A/B knob).  At least 3 slabs per part (the rows are loaded and normalised once per part).
-    static int split = -1;
-    if (split < 0) { const char* e = getenv("V3D_LNPROJ_SPLIT"); split = e ? atoi(e) : 1; }
+    // full.  At least 3 slabs per part (the rows are loaded and normalised once per part).
     int grid = nblocks < cus ? (int)nblocks : cus;
     p.full = (int)(nblocks / grid);
     p.tail_blocks = (int)(nblocks - (long long)p.full * grid);
     p.parts = 1;
     if (p.tail_blocks == 0 && p.full > 0) { p.full -= 1; p.tail_blocks = grid; }      // (uniform form: the last round is the "tail" of one whole part per block)
-    if (split && p.tail_blocks > 0) {
+    if (p.tail_blocks > 0) {
         int parts = cus / p.tail_blocks, maxp = (N / 64) / 3;
         if (parts > maxp) parts = maxp;
         if (parts < 1) parts = 1;
         p.parts = parts;
         if (p.full == 0) grid = p.tail_blocks * parts;
     }
-    if (big && cfg == 0) {
-        if (tl) hipLaunchKernelGGL((ln_proj_kernel<320, 4, 2, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, p);
-        else hipLaunchKernelGGL((ln_proj_kernel<320, 4, 2>), dim3(grid), dim3(256), 0, (hipStream_t)stream, p);
-    } else if (big) {
-        if (tl) hipLaunchKernelGGL((ln_proj_kernel<320, 8, 1, true>), dim3(grid), dim3(512), 0, (hipStream_t)stream, p);
-        else hipLaunchKernelGGL((ln_proj_kernel<320, 8, 1>), dim3(grid), dim3(512), 0, (hipStream_t)stream, p);
-    } else {
-        hipLaunchKernelGGL((ln_proj_kernel<320, 4, 1>), dim3(grid), dim3(256), 0, (hipStream_t)stream, p);
-    }
+    if (big)
+        hipLaunchKernelGGL((ln_proj_kernel<320, 8>), dim3(grid), dim3(512), 0, (hipStream_t)stream, p);
+    else
+        hipLaunchKernelGGL((ln_proj_kernel<320, 4>), dim3(grid), dim3(256), 0, (hipStream_t)stream, p);
     return v3d_check_launch("v3d_ln_proj");
 }

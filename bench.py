@@ -1,6 +1,6 @@
 """bench.py — V3D_512 dense-multi-view generation throughput on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--shard replica|frames]     (N > 1: launched by torch.distributed.run, one rank per GPU)
+    python bench.py --gpus N --steps K --warmup W [--shard replica|frames] [--full]     (N > 1: launched by torch.distributed.run, one rank per GPU)
 
 One "step" = one pass of the hot path over one batch: a full 18-frame sample — 25 EulerEDM steps (each one
 denoiser evaluation of the cfg-doubled 36-image batch through VideoUNet) followed by the 18-frame VideoDecoder decode
@@ -9,13 +9,14 @@ already resident in HBM).  metric = multi-view frames / second.
 
 Multi-GPU modes (--gpus N > 1):
   --shard replica (default)  every rank generates its own sample (independent inputs, no data-path collective): weak scaling,
-                             value = N * K * 18 / max-over-ranks time.  After the timed region the SAME job is also measured in
-                             frame-sharded mode and reported as the extra object "frame_shard" (it never changes `value`).
+                             value = N * K * 18 / max-over-ranks time.  With --full, after the timed region the SAME job is also
+                             measured in frame-sharded mode and reported as the extra object "frame_shard" (it never changes `value`).
   --shard frames             BASELINE.json configs[2]/[3]: ONE sample, its 18 frames sharded over the N ranks for the whole path
                              (v3d_amd/dist.py: K|V exchange before each temporal attention, +-1 frame halos for the (3,1,1) convs,
                              all-reduced 3-D GroupNorm sums; weights replicated): strong scaling, value = K * 18 / max-over-ranks time.
 
-Also reported on the same JSON line:
+A plain run sets up, warms up, times the K steps, writes --dump-outputs if asked and prints the result line; nothing else.
+With --full the same line also carries what takes runs of its own after the timed steps:
   roofline     — for the dominant kernel family (the `v3d_gemm` launches + the fused feed-forward): algorithmic FLOPs / summed launch
                  durations measured LIVE with HIP events on the launch stream in one extra instrumented sample, against the dense bf16
                  MFMA peak; `per_kernel` lists every timed op family of that sample with its own bound (mfma / hbm), achieved rate and
@@ -25,6 +26,7 @@ Also reported on the same JSON line:
   cpu_baseline — the fp32 CPU oracle (oracle/sgm_oracle.py, kind "port") timed on the host cores on a bounded sample of
                  the same workload and extrapolated (rank 0, N = 1 only), plus parity of the HIP path against it: one full-width
                  evaluation on the timed inputs and the 25-step width-64 rollout (latent cosine, decoded-frame PSNR).
+  frame_shard  — N > 1 replica mode: the frame-sharded measurement of the same job described above.
 """
 from __future__ import annotations
 
@@ -563,7 +565,25 @@ def make_step_latents(wrapped, sampler, denoiser, noise, c, uc, device):
     return sampler(lambda i, s, cc: denoiser(wrapped, i, s, cc, **extra), noise, cond=c, uc=uc)
 
 
-def main():
+def extra_legs(args, headline, world, shard_mode):
+    """The measurements a run makes after its timed steps, beyond the result line itself: none without --full.  `roofline` runs on
+    rank 0 for every workload; `frame_shard` is the secondary frame-sharded run of an N > 1 replica headline; `cpu_baseline` and its
+    `parity_rollout` belong to the one-GPU headline."""
+    if not args.full:
+        return set()
+    legs = set()
+    if not args.no_roofline:
+        legs.add("roofline")
+    if world > 1 and not shard_mode and headline:
+        legs.add("frame_shard")
+    if world == 1 and headline and not args.no_cpu_baseline:
+        legs.add("cpu_baseline")
+        if not args.no_parity_rollout:
+            legs.add("parity_rollout")
+    return legs
+
+
+def arg_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2)
@@ -577,11 +597,15 @@ def main():
     ap.add_argument("--fp8", action="store_true", help="scene workload: fp8 (OCP e4m3) spatial self-attention (V3D_ATTN_FP8=1)")
     ap.add_argument("--inputs", type=int, default=1, help="inputs per sample step (BASELINE.json configs[3]: batch-of-4 inputs); frames per step = inputs x frames")
     ap.add_argument("--edm-steps", dest="edm_steps", type=int, default=STEPS, help="EDM sampler steps (configs[3]: 50)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-parity-rollout", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what the result line does not need, each in a run of its own: the per-kernel "
+                         "roofline (one instrumented sample + a live clock probe), the fp32 CPU baseline with its parity legs (one GPU, "
+                         "headline workload) and the frame-sharded secondary run (N > 1, replica mode)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and its parity legs")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the roofline")
+    ap.add_argument("--no-parity-rollout", action="store_true", help="with --full: skip the 25-step parity rollout of the CPU baseline")
     ap.add_argument("--shard-timeout", dest="shard_timeout", type=float, default=240.0,
-                    help="N > 1 replica mode: seconds the secondary frame-sharded run may take before the line is printed without it")
+                    help="N > 1 replica mode with --full: seconds the secondary frame-sharded run may take before the line is printed without it")
     ap.add_argument("--shard-sim", dest="shard_sim", type=int, default=0,
                     help="N: measure on THIS GPU what rank 0 (most frames) and rank N-1 (fewest) of an N-GPU frame-sharded run compute per evaluation / decode "
                          "(self-fed exchanges, no communication) and the compute-only strong-scaling ceiling; prints its own JSON line and exits")
@@ -591,6 +615,11 @@ def main():
     ap.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step returned (the decoded frames, rank 0) to DIR/<name>.npy in float32, "
                          "at most 64 MB in all (a larger output becomes a fixed seeded sample of its elements, DIR/<name>_sample.npy)")
+    return ap
+
+
+def main():
+    ap = arg_parser()
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
@@ -620,6 +649,7 @@ def main():
     headline = not scene and B_IN == 1 and E_STEPS == STEPS          # roofline / cpu_baseline / parity legs belong to the headline workload
     unet, wrapped, dec, sampler, denoiser = build_models(device, steps=E_STEPS, frames=T_FR)
     shard_mode = args.shard in ("frames", "hybrid") and world > 1
+    legs = extra_legs(args, headline, world, shard_mode)
     # replica mode: every rank generates its own sample (different seed per rank); frame-shard mode: ONE sample, same inputs everywhere
     noise, c, uc = synth.synthetic_conditioning(T_FR, LH, LW, seed=23 + (0 if shard_mode else rank), device=device, batch=B_IN)
     if args.shard_sim:
@@ -718,12 +748,13 @@ def main():
                 "sent_MB_per_sample_rank0": round(cnt["bytes_sent"] / (args.steps + args.warmup) / 1e6, 1),
                 "note": "one grouped point-to-point launch per temporal norm + conv (raw halo + fp64 statistics) and per temporal attention (K|V); "
                         "NO RCCL timing of this path existed before this run: the build boxes have one GPU"}
-    if rank == 0 and not args.no_roofline and headline:
+        if headline:
+            result["config"]["hip_graph"] = bool(args.graph)
+    if rank == 0 and "roofline" in legs and headline:
         # per-launch HIP events need the launches to come from Python: the instrumented sample runs un-captured (and un-sharded)
         noise0, c0, uc0 = synth.synthetic_conditioning(T_FRAMES, LAT, LAT, seed=23, device=device)
         result["roofline"] = measure_rooflines(make_step(wrapped, dec, sampler, denoiser, noise0, c0, uc0, device, graph=False))
-        result["config"]["hip_graph"] = bool(args.graph)
-    elif rank == 0 and not args.no_roofline:
+    elif rank == 0 and "roofline" in legs:
         # other workloads: the same live per-op-family table (its own bounds); the fp8 attention family is priced against the fp8 MFMA peak
         noise0, c0, uc0 = synth.synthetic_conditioning(T_FR, LH, LW, seed=23, device=device, batch=B_IN)
         rl = measure_rooflines(make_step(wrapped, dec, sampler, denoiser, noise0, c0, uc0, device, graph=False, frames=T_FR, inputs=B_IN))
@@ -739,7 +770,7 @@ def main():
     #      number and its exchanges (grouped RCCL P2P between all ranks) must never cost the run its replica result - if it has not
     #      finished in time, rank 0 prints the line it has and every rank leaves without waiting for the others ----
     printed = [False]
-    if world > 1 and not shard_mode and headline:
+    if "frame_shard" in legs:
         import threading
 
         def bail():
@@ -776,12 +807,12 @@ def main():
         finally:
             watchdog.cancel()
         return
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and headline:
+    if rank == 0 and "cpu_baseline" in legs:
         try:
             result["cpu_baseline"] = cpu_baseline(unet, dec)
         except Exception as e:  # the baseline is informational; never lose the GPU number to a host-side failure
             result["cpu_baseline"] = {"value": None, "unit": "frames/s", "cores": torch.get_num_threads(), "kind": "port", "sample": f"failed: {e}"}
-        if not args.no_parity_rollout:
+        if "parity_rollout" in legs:
             try:
                 del unet, wrapped, dec
                 result["cpu_baseline"]["parity_rollout"] = parity_rollout(device)

@@ -14,6 +14,7 @@ def _last_json_line(path):
 
 
 def test_committed_bench_lines_keep_the_contract():
+    """The committed logs are full runs (`bench.py --full`): a plain run's line carries the same fields without roofline / cpu_baseline."""
     import re
     logs = sorted(f for f in glob.glob(os.path.join(ROOT, "profiles", "r0*_bench.log")) if re.fullmatch(r"r0\d[a-z]?_bench\.log", os.path.basename(f)))
     assert logs, "no committed bench log"
@@ -75,3 +76,29 @@ def test_pmc_profile_bench_reads_is_committed_and_not_older_than_the_kernels():
         f"profiles/{bench.PMC_PROFILE} was taken on kernel sources {prof.get('csrc_sha256_16')}, the tree is at {bench.csrc_digest()}: re-profile"
     tag = bench.PMC_PROFILE.split("_")[0]
     assert glob.glob(os.path.join(ROOT, "profiles", f"{tag}*_kernel_stats*.txt")), "kernel-trace summary of the same round missing"
+
+
+def test_a_plain_run_measures_nothing_beyond_its_steps_and_full_measures_the_rest():
+    """bench.py without --full times its steps and prints; the roofline, the CPU baseline with its parity legs and the frame-sharded
+    secondary run of an N > 1 replica job happen only with --full (each --no-* option still drops its leg there)."""
+    import sys
+    sys.path.insert(0, ROOT)
+    import bench
+    ap = bench.arg_parser()
+
+    def legs(argv, headline=True, world=1, shard_mode=False):
+        return bench.extra_legs(ap.parse_args(argv), headline, world, shard_mode)
+
+    plain = ["--gpus", "1", "--steps", "2", "--warmup", "1"]
+    assert not ap.parse_args(plain).full
+    assert legs(plain) == set()
+    assert legs(plain + ["--dump-outputs", "d"]) == set()
+    assert legs(["--workload", "scene"], headline=False) == set()
+    assert legs(["--gpus", "8"], world=8) == set()
+    assert legs(plain + ["--full"]) == {"roofline", "cpu_baseline", "parity_rollout"}
+    assert legs(plain + ["--full", "--no-parity-rollout"]) == {"roofline", "cpu_baseline"}
+    assert legs(plain + ["--full", "--no-cpu-baseline"]) == {"roofline"}
+    assert legs(plain + ["--full", "--no-roofline", "--no-cpu-baseline"]) == set()
+    assert legs(["--workload", "scene", "--full"], headline=False) == {"roofline"}
+    assert legs(["--gpus", "8", "--full"], world=8) == {"roofline", "frame_shard"}
+    assert legs(["--gpus", "8", "--shard", "frames", "--full"], world=8, shard_mode=True) == {"roofline"}

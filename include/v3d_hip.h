@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define V3D_ABI_VERSION 8
+#define V3D_ABI_VERSION 9
 
 typedef void* v3d_stream_t; /* hipStream_t */
 
@@ -352,6 +352,72 @@ int v3d_randn_add(const float* x, float scale, uint64_t seed, uint32_t call, flo
 int v3d_lincomb_f32(const float* const* src, const float* coef, int32_t nterms, float* out, int64_t n, v3d_stream_t stream);
 /* dst_bf16[r][dst_off + c] = src_bf16[r][src_off + c], c < C  (strided 2-D bf16 copy; C % 8 == 0) */
 int v3d_copy2d_bf16(const void* src, int64_t lds, void* dst, int64_t ldd, int64_t rows, int64_t C, v3d_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Gaussian-splat reconstruction (ABI 9; v3d_amd/recon/, csrc/gs.hip): the 3-D Gaussian splatting rasterizer (forward + backward) the
+ * reference's recon/train_from_vid.py calls through diff_gaussian_rasterization (recon/gaussian_renderer/__init__.py), the kNN of its
+ * initial scales (simple_knn distCUDA2, recon/scene/gaussian_model.py) and its D-SSIM + L1 loss (recon/utils/loss_utils.py).
+ * Per-Gaussian arrays are fp32 row-major [P][k]; SH degree 0 only.  No atomics: every result is bit-reproducible.
+ * Pipeline of one view: preprocess_fwd -> scan(tiles_touched) -> duplicate_keys -> radix_sort_pairs -> tile_ranges -> render_fwd;
+ * backward: render_bwd -> reduce_instance_grads -> preprocess_bwd.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct v3d_gs_camera {
+    float view[16];         /* world -> view, row-vector convention: p_view = [x y z 1] . view (the reference's world_view_transform) */
+    float proj[16];         /* world -> clip, same convention (the reference's full_proj_transform) */
+    float tanfovx, tanfovy; /* tan(fov / 2) */
+    float bg[3];            /* background colour */
+    int32_t width, height;  /* image size in pixels; 16 x 16 tiles, ragged at the right / bottom edge */
+} v3d_gs_camera;           /* HOST pointer in every entry below */
+
+/* out[i] = mean squared distance from point i to its 3 nearest other points (exact brute force; n >= 4); xyz [n][3] */
+int v3d_gs_knn3(const float* xyz, int64_t n, float* out, v3d_stream_t stream);
+/* Per Gaussian: activations (exp scale, normalised quaternion, sigmoid opacity, max(0, 0.5 + C0 dc)), EWA projection with the 0.3 dilation,
+ * conic, 3-sigma radius, tile rectangle.  Outputs: means2d [P][2] pixels, conic_opacity [P][4] (A, B, C, opacity) with
+ * power = -0.5 (A dx^2 + C dy^2) - B dx dy, rgb [P][3], depth [P] (view z), radii [P] (0 = culled), tiles_touched [P], clamped [P]
+ * (bit c set when colour channel c was clamped at 0). */
+int v3d_gs_preprocess_fwd(const float* xyz, const float* scale_raw, const float* rot_raw, const float* opacity_raw, const float* f_dc, int64_t P,
+                          const v3d_gs_camera* cam, float* means2d, float* conic_opacity, float* rgb, float* depth, int32_t* radii,
+                          int32_t* tiles_touched, int32_t* clamped, v3d_stream_t stream);
+/* out[0..n) = exclusive prefix sum of in (int32), out[n] = total; work: v3d_gs_scan_work_bytes(n) device bytes */
+int64_t v3d_gs_scan_work_bytes(int64_t n);
+int v3d_gs_scan(const int32_t* in, int64_t n, int32_t* out, void* work, int64_t work_bytes, v3d_stream_t stream);
+/* For every visible Gaussian g and every tile of its rectangle (row-major): keys[offsets[g] + k] = tile << 32 | float bits of depth[g],
+ * vals[...] = g; offsets = the scan of tiles_touched (P + 1 entries) */
+int v3d_gs_duplicate_keys(const float* means2d, const int32_t* radii, const float* depth, const int32_t* offsets, int64_t P, int32_t width,
+                          int32_t height, uint64_t* keys, uint32_t* vals, v3d_stream_t stream);
+/* Stable LSD radix sort of (uint64 key, uint32 value) pairs on the low nbits bits of the key (8-bit digits, ranks from wave ballots,
+ * no atomics); out-of-place; work: v3d_gs_sort_work_bytes(n) device bytes */
+int64_t v3d_gs_sort_work_bytes(int64_t n);
+int v3d_gs_radix_sort_pairs(const uint64_t* keys_in, const uint32_t* vals_in, uint64_t* keys_out, uint32_t* vals_out, int64_t n, int32_t nbits,
+                            void* work, int64_t work_bytes, v3d_stream_t stream);
+/* ranges [tiles][2] = [start, end) of every tile in the sorted list (zero for empty tiles); inst_pos [n_inst] = sorted position of every
+ * instance in duplicate_keys order (the sort permutation, recovered from the sorted Gaussian ids and their tile rectangles) */
+int v3d_gs_tile_ranges(const uint64_t* keys_sorted, const uint32_t* vals_sorted, int64_t n_inst, const float* means2d, const int32_t* radii,
+                       const int32_t* offsets, int32_t width, int32_t height, int32_t* ranges, int32_t* inst_pos, v3d_stream_t stream);
+/* One 256-thread block per 16 x 16 tile, front-to-back alpha blending: out_img [3][H][W], final_T [H][W], n_contrib [H][W] */
+int v3d_gs_render_fwd(const int32_t* ranges, const uint32_t* vals_sorted, const float* means2d, const float* conic_opacity, const float* rgb,
+                      const v3d_gs_camera* cam, float* out_img, float* final_T, int32_t* n_contrib, v3d_stream_t stream);
+/* Back to front per tile: inst_grads [n_inst][9] = the sorted instance's dL/d(mean2d x, y [pixels], conic A, B, C, opacity, r, g, b) summed
+ * over its tile's pixels in a fixed order (every slot is written) */
+int v3d_gs_render_bwd(const int32_t* ranges, const uint32_t* vals_sorted, const float* means2d, const float* conic_opacity, const float* rgb,
+                      const v3d_gs_camera* cam, const float* final_T, const int32_t* n_contrib, const float* dL_dimg, float* inst_grads,
+                      v3d_stream_t stream);
+/* grads9 [P][9] = sum over Gaussian g's instances u = offsets[g] .. offsets[g+1]-1, in that order, of inst_grads[inst_pos[u]] */
+int v3d_gs_reduce_instance_grads(const float* inst_grads, const int32_t* offsets, const int32_t* inst_pos, int64_t P, float* grads9,
+                                 v3d_stream_t stream);
+/* Chain rule to the raw parameters: d_xyz [P][3], d_scale_raw [P][3] (log scale), d_rot_raw [P][4] (unnormalised quaternion),
+ * d_opacity_raw [P] (pre-sigmoid), d_f_dc [P][3]; d_means2d [P][2] = dL/d(NDC mean), the reference's viewspace_points.grad[:, :2] */
+int v3d_gs_preprocess_bwd(const float* xyz, const float* scale_raw, const float* rot_raw, const float* opacity_raw, int64_t P,
+                          const v3d_gs_camera* cam, const int32_t* radii, const int32_t* clamped, const float* grads9, float* d_xyz,
+                          float* d_scale_raw, float* d_rot_raw, float* d_opacity_raw, float* d_f_dc, float* d_means2d, v3d_stream_t stream);
+/* loss = (1 - lambda) mean|img - gt| + lambda (1 - SSIM(img, gt)), SSIM with the 11-tap sigma-1.5 window, zero padding, per channel;
+ * img / gt [C][H][W]; out3 = (loss, ssim, l1) on the device; work: v3d_gs_ssim_work_floats(C, H, W) floats, kept for the backward */
+int64_t v3d_gs_ssim_work_floats(int32_t C, int32_t H, int32_t W);
+int v3d_gs_ssim_l1_fwd(const float* img, const float* gt, int32_t C, int32_t H, int32_t W, float lambda_dssim, float* work, int64_t work_floats,
+                       float* out3, v3d_stream_t stream);
+/* grad [C][H][W] = dloss[0] * dloss/dimg (dloss: device scalar), from the work buffer of the forward call on the same images */
+int v3d_gs_ssim_l1_bwd(const float* img, const float* gt, int32_t C, int32_t H, int32_t W, float lambda_dssim, float* work, int64_t work_floats,
+                       const float* dloss, float* grad, v3d_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,52 @@
+"""Timing of the reconstruction step (v3d_amd/recon/) at the documented settings: 18-view 512 x 512 orbit, --sh_degree 0 --lambda_dssim 1.0
+--lambda_lpips 0 --num_pts 100000 -w, 4000 iterations.  The orbit is a seeded 3000-Gaussian scene rendered by the HIP forward (no
+checkpoints needed).  Prints one JSON line: total seconds, ms per iteration, Gaussian count after densification, final training-view PSNR.
+
+    python tools/recon_bench.py [--iterations 4000] [--reso 512]
+    rocprofv3 --kernel-trace --stats -d /tmp/rp -o rp -- python tools/recon_bench.py --iterations 300     # per-kernel split
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for _p in (ROOT, os.path.join(ROOT, "tests")):
+    if _p not in sys.path:
+        sys.path.insert(0, _p)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iterations", type=int, default=4000)
+    ap.add_argument("--reso", type=int, default=512)
+    ap.add_argument("--views", type=int, default=18)
+    ap.add_argument("--num_pts", type=int, default=100_000)
+    a = ap.parse_args()
+    import gs_dense_ref as D
+    from v3d_amd.recon import rasterize as RZ
+    from v3d_amd.recon import train as TR
+    from v3d_amd.recon.cameras import orbit_cameras
+    scene = [t.cuda() for t in D.random_scene(3000, 11, spread=0.3)]
+    cams, _ = orbit_cameras(a.views, 2.0, 0.0, 60.0, a.reso)
+    with torch.no_grad():
+        frames = torch.stack([(RZ.rasterize(*scene, c, [1, 1, 1])[0].clamp(0, 1) * 255).round().to(torch.uint8).permute(1, 2, 0) for c in cams])
+    TR.reconstruct(frames[:, :64, :64].contiguous(), iterations=20, num_pts=1000, white_background=True)      # warm-up (library load, allocator)
+    g, cams, st = TR.reconstruct(frames, iterations=a.iterations, lambda_dssim=1.0, lambda_lpips=0.0, num_pts=a.num_pts, white_background=True,
+                                 seed=0)
+    gt = frames.permute(0, 3, 1, 2).float() / 255.0
+    bg = torch.ones(3, device="cuda")
+    with torch.no_grad():
+        ps = [TR.psnr(RZ.render(c, g, bg)["render"].clamp(0, 1), gt[i]) for i, c in enumerate(cams)]
+    print(json.dumps({"iterations": a.iterations, "reso": a.reso, "views": a.views, "num_pts": a.num_pts, "seconds": round(st["seconds"], 2),
+                      "ms_per_iter": round(1000 * st["seconds"] / a.iterations, 3), "num_gaussians": st["num_gaussians"],
+                      "psnr_mean": round(float(np.mean(ps)), 2), "device": torch.cuda.get_device_name(0)}))
+
+
+if __name__ == "__main__":
+    main()

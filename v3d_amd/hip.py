@@ -16,7 +16,7 @@ from .ops import GemmCall, OpsBase
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("V3D_HIP_LIB") or os.path.join(_HERE, "lib", "libv3d_hip.so")     # (override: A/B runs of two builds on one box)
 
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 c_i64, c_i32, c_f32, c_f64, c_vp = C.c_int64, C.c_int32, C.c_float, C.c_double, C.c_void_p
 
@@ -43,6 +43,14 @@ class _GemmArgs(C.Structure):
         ("A2", c_vp), ("K1", c_i64), ("lda2", c_i64),
     ]
 
+
+class GsCamera(C.Structure):
+    """Mirror of `v3d_gs_camera` (include/v3d_hip.h); passed by host pointer."""
+    _fields_ = [("view", c_f32 * 16), ("proj", c_f32 * 16), ("tanfovx", c_f32), ("tanfovy", c_f32), ("bg", c_f32 * 3),
+                ("width", c_i32), ("height", c_i32)]
+
+
+_CAM = C.POINTER(GsCamera)
 
 # name -> (restype, argtypes); must list every symbol declared in include/v3d_hip.h
 SIGNATURES = {
@@ -93,6 +101,21 @@ SIGNATURES = {
     "v3d_copy2d_bf16": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i64, c_i64, c_vp]),
     "v3d_randn_add": (c_i32, [c_vp, c_f32, C.c_uint64, C.c_uint32, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_vp]),
     "v3d_lincomb_f32": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_i64, c_vp]),
+    "v3d_gs_knn3": (c_i32, [c_vp, c_i64, c_vp, c_vp]),
+    "v3d_gs_preprocess_fwd": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, _CAM, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "v3d_gs_scan_work_bytes": (c_i64, [c_i64]),
+    "v3d_gs_scan": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_i64, c_vp]),
+    "v3d_gs_duplicate_keys": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    "v3d_gs_sort_work_bytes": (c_i64, [c_i64]),
+    "v3d_gs_radix_sort_pairs": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_vp, c_i64, c_vp]),
+    "v3d_gs_tile_ranges": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    "v3d_gs_render_fwd": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, _CAM, c_vp, c_vp, c_vp, c_vp]),
+    "v3d_gs_render_bwd": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, _CAM, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "v3d_gs_reduce_instance_grads": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp]),
+    "v3d_gs_preprocess_bwd": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, _CAM, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "v3d_gs_ssim_work_floats": (c_i64, [c_i32, c_i32, c_i32]),
+    "v3d_gs_ssim_l1_fwd": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_f32, c_vp, c_i64, c_vp, c_vp]),
+    "v3d_gs_ssim_l1_bwd": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_f32, c_vp, c_i64, c_vp, c_vp, c_vp]),
 }
 
 
@@ -715,3 +738,129 @@ class HipOps(OpsBase):
         self._check(self.lib.v3d_copy2d_bf16(src.data_ptr(), src.stride(0), dst.data_ptr(), dst.stride(0), rows, Cc, self._stream()),
                     "v3d_copy2d_bf16")
         return dst
+
+    # ---- Gaussian-splat reconstruction (csrc/gs.hip; v3d_amd/recon/rasterize.py composes these) ----------------------------------
+    def gs_knn3(self, xyz):
+        """Mean squared distance of every point to its 3 nearest other points (exact), xyz fp32 [n, 3]."""
+        self._req_c(xyz, torch.float32, "gs_knn3.xyz")
+        out = torch.empty(xyz.shape[0], dtype=torch.float32, device=xyz.device)
+        self._check(self.lib.v3d_gs_knn3(xyz.data_ptr(), xyz.shape[0], out.data_ptr(), self._stream()), "v3d_gs_knn3")
+        return out
+
+    def gs_preprocess_fwd(self, xyz, scale_raw, rot_raw, opacity_raw, f_dc, cam: "GsCamera"):
+        P = xyz.shape[0]
+        for t, k, nm in ((xyz, 3, "xyz"), (scale_raw, 3, "scale"), (rot_raw, 4, "rot"), (opacity_raw, 1, "opacity"), (f_dc, 3, "f_dc")):
+            self._req_c(t, torch.float32, f"gs_preprocess_fwd.{nm}")
+            if t.numel() != P * k:
+                raise RuntimeError(f"gs_preprocess_fwd: {nm} has {t.numel()} values, expected {P} x {k}")
+        d, f32, i32 = xyz.device, torch.float32, torch.int32
+        o = {"means2d": torch.empty(P, 2, dtype=f32, device=d), "conic_opacity": torch.empty(P, 4, dtype=f32, device=d),
+             "rgb": torch.empty(P, 3, dtype=f32, device=d), "depth": torch.empty(P, dtype=f32, device=d),
+             "radii": torch.empty(P, dtype=i32, device=d), "tiles": torch.empty(P, dtype=i32, device=d), "clamped": torch.empty(P, dtype=i32, device=d)}
+        self._check(self.lib.v3d_gs_preprocess_fwd(xyz.data_ptr(), scale_raw.data_ptr(), rot_raw.data_ptr(), opacity_raw.data_ptr(), f_dc.data_ptr(), P,
+                                                   C.byref(cam), *(o[k].data_ptr() for k in ("means2d", "conic_opacity", "rgb", "depth", "radii", "tiles",
+                                                                                           "clamped")), self._stream()), "v3d_gs_preprocess_fwd")
+        return o
+
+    def gs_scan(self, x):
+        """Exclusive int32 prefix sum: returns [n + 1] (last entry = total)."""
+        self._req_c(x, torch.int32, "gs_scan.x")
+        n = x.numel()
+        out = torch.empty(n + 1, dtype=torch.int32, device=x.device)
+        wb = self.lib.v3d_gs_scan_work_bytes(n)
+        work = torch.empty(max(wb, 4), dtype=torch.uint8, device=x.device)
+        self._check(self.lib.v3d_gs_scan(x.data_ptr(), n, out.data_ptr(), work.data_ptr(), wb, self._stream()), "v3d_gs_scan")
+        return out
+
+    def gs_duplicate_keys(self, means2d, radii, depth, offsets, n_inst, width, height):
+        P = radii.numel()
+        keys = torch.empty(n_inst, dtype=torch.int64, device=radii.device)
+        vals = torch.empty(n_inst, dtype=torch.int32, device=radii.device)
+        if n_inst:
+            self._check(self.lib.v3d_gs_duplicate_keys(means2d.data_ptr(), radii.data_ptr(), depth.data_ptr(), offsets.data_ptr(), P, int(width),
+                                                       int(height), keys.data_ptr(), vals.data_ptr(), self._stream()), "v3d_gs_duplicate_keys")
+        return keys, vals
+
+    def gs_radix_sort_pairs(self, keys, vals, nbits):
+        """Stable sort of (uint64 key, uint32 value) pairs (held in int64 / int32 tensors) on the low `nbits` key bits."""
+        self._req_c(keys, torch.int64, "gs_sort.keys")
+        self._req_c(vals, torch.int32, "gs_sort.vals")
+        n = keys.numel()
+        if vals.numel() != n:
+            raise RuntimeError(f"gs_radix_sort_pairs: {n} keys vs {vals.numel()} values")
+        ko, vo = torch.empty_like(keys), torch.empty_like(vals)
+        if n == 0:
+            return ko, vo
+        wb = self.lib.v3d_gs_sort_work_bytes(n)
+        work = torch.empty(wb, dtype=torch.uint8, device=keys.device)
+        self._check(self.lib.v3d_gs_radix_sort_pairs(keys.data_ptr(), vals.data_ptr(), ko.data_ptr(), vo.data_ptr(), n, int(nbits), work.data_ptr(), wb,
+                                                     self._stream()), "v3d_gs_radix_sort_pairs")
+        return ko, vo
+
+    def gs_tile_ranges(self, keys_s, vals_s, means2d, radii, offsets, width, height):
+        n = keys_s.numel()
+        ntiles = ((width + 15) // 16) * ((height + 15) // 16)
+        ranges = torch.empty(ntiles, 2, dtype=torch.int32, device=radii.device)
+        inst_pos = torch.empty(n, dtype=torch.int32, device=radii.device)
+        self._check(self.lib.v3d_gs_tile_ranges(_ptr(keys_s) if n else None, _ptr(vals_s) if n else None, n, means2d.data_ptr(), radii.data_ptr(),
+                                                offsets.data_ptr(), int(width), int(height), ranges.data_ptr(), _ptr(inst_pos) if n else None,
+                                                self._stream()), "v3d_gs_tile_ranges")
+        return ranges, inst_pos
+
+    def gs_render_fwd(self, ranges, vals_s, means2d, conic_opacity, rgb, cam: "GsCamera"):
+        d, H, W = rgb.device, cam.height, cam.width
+        img = torch.empty(3, H, W, dtype=torch.float32, device=d)
+        final_T = torch.empty(H, W, dtype=torch.float32, device=d)
+        n_contrib = torch.empty(H, W, dtype=torch.int32, device=d)
+        self._check(self.lib.v3d_gs_render_fwd(ranges.data_ptr(), _ptr(vals_s) if vals_s.numel() else None, means2d.data_ptr(), conic_opacity.data_ptr(),
+                                               rgb.data_ptr(), C.byref(cam), img.data_ptr(), final_T.data_ptr(), n_contrib.data_ptr(), self._stream()),
+                    "v3d_gs_render_fwd")
+        return img, final_T, n_contrib
+
+    def gs_render_bwd(self, ranges, vals_s, means2d, conic_opacity, rgb, cam: "GsCamera", final_T, n_contrib, dimg):
+        self._req_c(dimg, torch.float32, "gs_render_bwd.dimg")
+        n = vals_s.numel()
+        inst = torch.empty(n, 9, dtype=torch.float32, device=dimg.device)
+        self._check(self.lib.v3d_gs_render_bwd(ranges.data_ptr(), _ptr(vals_s) if n else None, means2d.data_ptr(), conic_opacity.data_ptr(), rgb.data_ptr(),
+                                               C.byref(cam), final_T.data_ptr(), n_contrib.data_ptr(), dimg.data_ptr(), _ptr(inst) if n else None,
+                                               self._stream()), "v3d_gs_render_bwd")
+        return inst
+
+    def gs_reduce_instance_grads(self, inst_grads, offsets, inst_pos, P):
+        g9 = torch.empty(P, 9, dtype=torch.float32, device=offsets.device)
+        n = inst_pos.numel()
+        self._check(self.lib.v3d_gs_reduce_instance_grads(_ptr(inst_grads) if n else None, offsets.data_ptr(), _ptr(inst_pos) if n else None, P,
+                                                          g9.data_ptr(), self._stream()), "v3d_gs_reduce_instance_grads")
+        return g9
+
+    def gs_preprocess_bwd(self, xyz, scale_raw, rot_raw, opacity_raw, cam: "GsCamera", radii, clamped, g9):
+        P, d, f32 = xyz.shape[0], xyz.device, torch.float32
+        o = {"xyz": torch.empty(P, 3, dtype=f32, device=d), "scale": torch.empty(P, 3, dtype=f32, device=d), "rot": torch.empty(P, 4, dtype=f32, device=d),
+             "opacity": torch.empty(P, 1, dtype=f32, device=d), "f_dc": torch.empty(P, 3, dtype=f32, device=d), "means2d": torch.empty(P, 2, dtype=f32, device=d)}
+        self._check(self.lib.v3d_gs_preprocess_bwd(xyz.data_ptr(), scale_raw.data_ptr(), rot_raw.data_ptr(), opacity_raw.data_ptr(), P, C.byref(cam),
+                                                   radii.data_ptr(), clamped.data_ptr(), g9.data_ptr(),
+                                                   *(o[k].data_ptr() for k in ("xyz", "scale", "rot", "opacity", "f_dc", "means2d")), self._stream()),
+                    "v3d_gs_preprocess_bwd")
+        return o
+
+    def gs_ssim_l1_fwd(self, img, gt, lambda_dssim):
+        """Fused (1 - lambda) L1 + lambda (1 - SSIM) of [C, H, W] images: returns (out3 = (loss, ssim, l1) on the device, work for the backward)."""
+        self._req_c(img, torch.float32, "gs_ssim.img")
+        self._req_c(gt, torch.float32, "gs_ssim.gt")
+        if img.dim() != 3 or img.shape != gt.shape:
+            raise RuntimeError(f"gs_ssim_l1_fwd: img {tuple(img.shape)} / gt {tuple(gt.shape)} must both be [C, H, W]")
+        Cc, H, W = img.shape
+        nw = self.lib.v3d_gs_ssim_work_floats(Cc, H, W)
+        work = torch.empty(nw, dtype=torch.float32, device=img.device)
+        out3 = torch.empty(3, dtype=torch.float32, device=img.device)
+        self._check(self.lib.v3d_gs_ssim_l1_fwd(img.data_ptr(), gt.data_ptr(), Cc, H, W, float(lambda_dssim), work.data_ptr(), nw, out3.data_ptr(),
+                                                self._stream()), "v3d_gs_ssim_l1_fwd")
+        return out3, work
+
+    def gs_ssim_l1_bwd(self, img, gt, lambda_dssim, work, dloss):
+        Cc, H, W = img.shape
+        self._req_c(dloss, torch.float32, "gs_ssim.dloss")
+        grad = torch.empty_like(img)
+        self._check(self.lib.v3d_gs_ssim_l1_bwd(img.data_ptr(), gt.data_ptr(), Cc, H, W, float(lambda_dssim), work.data_ptr(), work.numel(), dloss.data_ptr(),
+                                                grad.data_ptr(), self._stream()), "v3d_gs_ssim_l1_bwd")
+        return grad

@@ -411,7 +411,8 @@ int v3d_gs_preprocess_bwd(const float* xyz, const float* scale_raw, const float*
                           const v3d_gs_camera* cam, const int32_t* radii, const int32_t* clamped, const float* grads9, float* d_xyz,
                           float* d_scale_raw, float* d_rot_raw, float* d_opacity_raw, float* d_f_dc, float* d_means2d, v3d_stream_t stream);
 /* loss = (1 - lambda) mean|img - gt| + lambda (1 - SSIM(img, gt)), SSIM with the 11-tap sigma-1.5 window, zero padding, per channel;
- * img / gt [C][H][W]; out3 = (loss, ssim, l1) on the device; work: v3d_gs_ssim_work_floats(C, H, W) floats, kept for the backward */
+ * img / gt [C][H][W]; out3 = (loss, ssim, l1) on the device; work: v3d_gs_ssim_work_floats(C, H, W) floats,
+ * 8-byte aligned (it holds fp64 moment maps), kept for the backward */
 int64_t v3d_gs_ssim_work_floats(int32_t C, int32_t H, int32_t W);
 int v3d_gs_ssim_l1_fwd(const float* img, const float* gt, int32_t C, int32_t H, int32_t W, float lambda_dssim, float* work, int64_t work_floats,
                        float* out3, v3d_stream_t stream);

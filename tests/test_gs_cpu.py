@@ -230,3 +230,143 @@ def test_screen_size_prune_after_reset_interval():
     # as in the reference, the clone / split steps reset max_radii2D before the screen-size test, so only the world-size rule removes a point
     assert g.xyz.shape[0] == 5
     assert not torch.isclose(g.scaling[:, 0], torch.tensor(math.log(0.5))).any()
+
+
+# ---- the scenes of tests/test_gs_edges_gpu.py: what follows is the condition for those GPU tests meaning anything ------------------------
+EDGE_IDS = [D.case_id(c) for c in D.EDGE_CASES]
+
+
+@pytest.fixture(scope="module")
+def edge_oracles():
+    return D.EdgeOracles()
+
+
+def _view(cam, W, H):
+    return cam.world_view, cam.full_proj, cam.tanfovx, cam.tanfovy, W, H
+
+
+@pytest.mark.parametrize("case", D.EDGE_CASES, ids=EDGE_IDS)
+def test_edge_scenes_keep_their_margin(case):
+    _, _, W, H, _, _ = case
+    scene, cam, _ = D.edge_case(case)
+    m = D.scene_margins(*scene, *_view(cam, W, H))
+    assert min(v for k, v in m.items() if k != "depth_gap") >= D.SCENE_MARGIN, m
+    assert m["depth_gap"] >= D.DEPTH_GAP_MARGIN, m
+    assert m["transmittance"] >= D.DEEP_T_MARGIN, m
+
+
+def test_edge_cases_use_the_listed_seeds_and_ragged_sizes():
+    assert {c[1] for c in D.EDGE_CASES if c[0] == "deep"} == set(D.DEEP_SEEDS) and len(set(D.DEEP_SEEDS)) == 3
+    assert {c[1] for c in D.EDGE_CASES if c[0] == "cull"} == set(D.CULL_SEEDS)
+    for kind in ("deep", "cull", "tie"):
+        sizes = {(c[2], c[3]) for c in D.EDGE_CASES if c[0] == kind}
+        assert sizes & set(D.FORWARD_SIZES_RAGGED), kind
+    assert all(W % 16 and H % 16 for W, H in D.FORWARD_SIZES_RAGGED)
+    assert {(c[2], c[3]) for c in D.EDGE_CASES} >= set(D.FORWARD_SIZES_RAGGED)
+    assert any(c[2] % 16 == 0 and c[3] % 16 == 0 for c in D.EDGE_CASES)
+    assert all(c[2] * c[3] <= 64 * 64 for c in D.EDGE_CASES)
+
+
+@pytest.mark.parametrize("case", D.EDGE_CASES, ids=EDGE_IDS)
+def test_float32_oracle_agrees_with_float64_on_edge_scenes(edge_oracles, case):
+    # the GPU bars are 1e-4 on the image and 1e-3 relative L2 on every gradient: the number format itself may cost a quarter of each at most
+    c = edge_oracles(case)
+    (i64, p64, g64), (i32, p32, g32) = c["o64"], c["o32"]
+    assert (i32.double() - i64).abs().max().item() <= 2.5e-5
+    for name in D.GRAD_NAMES:
+        assert D.rel_l2(g32[name], g64[name]) <= 2.5e-4, name
+    # every decision falls the same way in both precisions
+    assert torch.equal(p32["visible"], p64["visible"]) and torch.equal(p32["n_contrib"], p64["n_contrib"])
+    assert torch.equal(p32["saturated"], p64["saturated"]) and torch.equal(p32["guarded"], p64["guarded"])
+    assert torch.equal(p32["radius"][p64["visible"]].double(), p64["radius"][p64["visible"]])
+    vis = p64["visible"]
+    assert (p32["depth"].double() - p64["depth"])[vis].abs().max().item() <= D.DEPTH_GAP_MARGIN / 4
+    # the error the float32 run makes on one Gaussian is the yardstick of the per-Gaussian bound of the GPU test: it must be a number
+    for name in ("xyz", "opacity"):
+        e, rows = D.per_gaussian_error(g32[name], g64[name])
+        assert 0 < e < 2.5e-4 and rows >= 9, (name, e, rows)
+
+
+def _tiles(W, H):
+    return [(ty, tx) for ty in range(0, H, D.TILE) for tx in range(0, W, D.TILE)]
+
+
+@pytest.mark.parametrize("case", [c for c in D.EDGE_CASES if c[0] == "deep"], ids=[i for i in EDGE_IDS if i.startswith("deep")])
+def test_deep_scenes_cover_long_lists_and_saturation(edge_oracles, case):
+    _, _, W, H, _, _ = case
+    _, pr, g64 = edge_oracles(case)["o64"]
+    assert int(pr["list_len"].max()) > 512                      # three forward batches of 256 and more
+    assert float(pr["saturated"].float().mean()) >= 0.05
+    assert bool((pr["saturated"] & (pr["n_contrib"] > 256)).any())      # a pixel that stops in a later batch than the first
+    # a tile whose last contributor lies more than one backward batch (64) before the end of its list: the backward zero-fills the rest
+    gaps = [int(pr["list_len"][ty, tx]) - int(pr["n_contrib"][ty:ty + D.TILE, tx:tx + D.TILE].max()) for ty, tx in _tiles(W, H)]
+    assert max(gaps) > 64, gaps
+    # a tile all of whose pixels have stopped (the block-wide early exit), and one where some pixels go on after others have stopped
+    sat = [bool(pr["saturated"][ty:ty + D.TILE, tx:tx + D.TILE].all()) for ty, tx in _tiles(W, H)]
+    assert any(sat) and not all(sat)
+    # Gaussians hidden behind saturation in every pixel: visible, yet their gradient is exactly zero
+    hidden = pr["visible"] & (g64["opacity"].reshape(-1) == 0)
+    assert int(hidden.sum()) >= 10
+
+
+@pytest.mark.parametrize("case", [c for c in D.EDGE_CASES if c[0] == "cull"], ids=[i for i in EDGE_IDS if i.startswith("cull")])
+def test_cull_groups_are_what_they_were_built_for(edge_oracles, case):
+    _, _, W, H, _, _ = case
+    c = edge_oracles(case)
+    _, pr, g64 = c["o64"]
+    gr, cam = c["groups"], c["cam"]
+    assert set(gr) == set(D.CULL_GROUPS) and all(v.numel() > 0 for v in gr.values())
+    gx, gy = (W + D.TILE - 1) // D.TILE, (H + D.TILE - 1) // D.TILE
+    vis, depth, rect = pr["visible"], pr["depth"], pr["rect"]
+    assert (depth[gr["behind"]] < 0).all() and not vis[gr["behind"]].any()
+    assert ((depth[gr["near"]] > 0) & (depth[gr["near"]] < 0.2)).all() and not vis[gr["near"]].any()
+    far = gr["far_out"]
+    assert (depth[far] > 0.2).all() and not vis[far].any()
+    assert (((rect[far, 2] - rect[far, 0]) * (rect[far, 3] - rect[far, 1])) == 0).all()
+    gd = gr["guard"]
+    outside = (pr["txtz"][gd].abs() > cam.tanfovx) | (pr["tytz"][gd].abs() > cam.tanfovy)
+    assert vis[gd].all() and pr["guarded"][gd].all() and outside.all()
+    assert (pr["txtz"][gd].abs() > 1.3 * cam.tanfovx).any() and (pr["tytz"][gd].abs() > 1.3 * cam.tanfovy).any()
+    assert (g64["xyz"][gd].norm(dim=1) > 0).all()           # each reaches the image and takes a gradient through the clamped Jacobian
+    assert not pr["guarded"][gr["huge"]].any() and not pr["guarded"][gr["dark"]].any()
+    hg = gr["huge"]
+    assert vis[hg].all() and (rect[hg] == torch.tensor([0, 0, gx, gy], dtype=rect.dtype)).all()
+    full = torch.stack([(pr["pix"][hg, 0] - pr["radius"][hg]) / D.TILE, (pr["pix"][hg, 1] - pr["radius"][hg]) / D.TILE], 1)
+    over = torch.stack([(pr["pix"][hg, 0] + pr["radius"][hg]) / D.TILE - gx, (pr["pix"][hg, 1] + pr["radius"][hg]) / D.TILE - gy], 1)
+    assert (full < 0).all() and (over > 0).all()              # clamped on all four sides, not just touching
+    dk = gr["dark"]
+    assert vis[dk].all() and (pr["rgb_raw"][dk] < 0).all() and (pr["rgb"][dk] == 0).all()
+    assert (g64["f_dc"][dk] == 0).all() and (g64["opacity"][dk].reshape(-1) != 0).all()
+    for name in D.GRAD_NAMES:       # culled: exactly zero everywhere
+        for k in ("behind", "near", "far_out"):
+            assert (g64[name][gr[k]] == 0).all(), (name, k)
+
+
+@pytest.mark.parametrize("case", [c for c in D.EDGE_CASES if c[2] % 16 or c[3] % 16], ids=[i for c, i in zip(D.EDGE_CASES, EDGE_IDS) if c[2] % 16 or c[3] % 16])
+def test_ragged_sizes_have_lit_pixels_in_partial_tiles(edge_oracles, case):
+    _, _, W, H, _, _ = case
+    _, pr, _ = edge_oracles(case)["o64"]
+    lit = pr["n_contrib"] > 0
+    if W % 16:
+        assert bool(lit[:, W - W % 16:].any())
+    if H % 16:
+        assert bool(lit[H - H % 16:, :].any())
+
+
+def test_tie_scene_depths_are_equal_and_their_order_matters():
+    scene, groups = D.tie_scene()
+    for W, H in {(c[2], c[3]) for c in D.EDGE_CASES if c[0] == "tie"}:
+        cam = D.axis_camera(W, H)
+        wv = cam.world_view
+        assert set(wv.flatten().tolist()) <= {0.0, 1.0, -1.0, 2.0} and wv[0, 2] == -1.0 and wv[3, 2] == 2.0      # view z = 2 - x, exactly
+        for dt in (torch.float32, torch.float64):
+            d = D.project(*scene, *_view(cam, W, H), dt)["depth"]
+            for g in groups:
+                assert (d[g] == d[g[0]]).all()
+            assert len(set(d.tolist())) == len(groups)
+        ref, pr = D.render(*scene, *_view(cam, W, H), [1.0, 1.0, 1.0])
+        assert pr["visible"].all()
+        for g in groups:      # the same Gaussians in another index order: a different image, by far more than the forward bar of 1e-4
+            for a, b in ((0, 1), (1, 2), (0, 2)):
+                swapped, _ = D.render(*D.swap_rows(scene, int(g[a]), int(g[b])), *_view(cam, W, H), [1.0, 1.0, 1.0])
+                assert (swapped - ref).abs().max().item() >= 100 * 1e-4, (W, H, g, a, b)

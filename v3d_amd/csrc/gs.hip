@@ -340,7 +340,8 @@ __device__ __forceinline__ unsigned long long peers_of(unsigned d, bool valid) {
     return peers;
 }
 
-__global__ void radix_count_kernel(const uint64_t* __restrict__ keys, long long n, int shift, long long nb, int32_t* __restrict__ counts) {
+__global__ void radix_count_kernel(const uint64_t* __restrict__ keys, long long n, int shift, unsigned dmask, long long nb,
+                                   int32_t* __restrict__ counts) {
     __shared__ int whist[NT / V3D_WAVE][RS_DIG];
     const int t = threadIdx.x, w = t / V3D_WAVE, lane = t % V3D_WAVE;
     for (int k = t; k < (NT / V3D_WAVE) * RS_DIG; k += NT) (&whist[0][0])[k] = 0;
@@ -349,7 +350,7 @@ __global__ void radix_count_kernel(const uint64_t* __restrict__ keys, long long 
     for (int sub = 0; sub < RS_SUB; ++sub) {
         const long long j = (long long)blockIdx.x * RS_CHUNK + sub * NT + t;
         const bool valid = j < n;
-        const unsigned d = valid ? (unsigned)((keys[j] >> shift) & (RS_DIG - 1)) : 0u;
+        const unsigned d = valid ? (unsigned)(keys[j] >> shift) & dmask : 0u;
         const unsigned long long peers = peers_of(d, valid);
         if (valid && (peers & lt) == 0) whist[w][d] += __popcll(peers);      // one leader lane per digit and wave
     }
@@ -359,8 +360,8 @@ __global__ void radix_count_kernel(const uint64_t* __restrict__ keys, long long 
     counts[(long long)t * nb + blockIdx.x] = s;        // digit-major: the exclusive scan gives stable global offsets
 }
 
-__global__ void radix_scatter_kernel(const uint64_t* __restrict__ kin, const uint32_t* __restrict__ vin, long long n, int shift, long long nb,
-                                     const int32_t* __restrict__ offs, uint64_t* __restrict__ kout, uint32_t* __restrict__ vout) {
+__global__ void radix_scatter_kernel(const uint64_t* __restrict__ kin, const uint32_t* __restrict__ vin, long long n, int shift, unsigned dmask,
+                                     long long nb, const int32_t* __restrict__ offs, uint64_t* __restrict__ kout, uint32_t* __restrict__ vout) {
     __shared__ int whist[NT / V3D_WAVE][RS_DIG];
     __shared__ int run[RS_DIG];
     const int t = threadIdx.x, w = t / V3D_WAVE, lane = t % V3D_WAVE;
@@ -373,7 +374,7 @@ __global__ void radix_scatter_kernel(const uint64_t* __restrict__ kin, const uin
         const bool valid = j < n;
         const uint64_t key = valid ? kin[j] : 0ull;
         const uint32_t val = valid ? vin[j] : 0u;
-        const unsigned d = (unsigned)((key >> shift) & (RS_DIG - 1));
+        const unsigned d = (unsigned)(key >> shift) & dmask;
         const unsigned long long peers = peers_of(d, valid);
         const int rank = __popcll(peers & lt);
         if (valid && rank == 0) whist[w][d] = __popcll(peers);
@@ -608,24 +609,26 @@ __global__ void reduce_grads_kernel(const float* __restrict__ inst_grads, const 
 // fused D-SSIM + L1.  Window: 11 taps, sigma 1.5, zero padding 5, per channel; the 2-D window is the outer product of the 1-D one.
 struct Win { float g[11]; };
 
-// horizontal pass: nmaps source maps built from (x, y) per mode
-template <int MODE>
+// horizontal pass: nmaps source maps built from (x, y) per mode.  The five moment maps of the forward (MODE 0) are accumulated and kept in
+// fp64: var = E[x^2] - E[x]^2 cancels to ~0 on flat image regions, and what fp32 moments leave of it (a few 1e-9) is not small beside
+// c2 = 9e-4 (a constant image pair was off by 3e-5 in SSIM)
+template <int MODE, typename TO>
 __global__ void ssim_hblur_kernel(const float* __restrict__ a, const float* __restrict__ b, long long C, int H, int W, Win win,
-                                  float* __restrict__ out) {
+                                  TO* __restrict__ out) {
     const long long CHW = C * H * W;
     const long long i = (long long)blockIdx.x * NT + threadIdx.x;
     if (i >= CHW) return;
     const int x = (int)(i % W);
     constexpr int NM = MODE == 0 ? 5 : 3;
-    float acc[NM];
-    for (int m = 0; m < NM; ++m) acc[m] = 0.f;
+    TO acc[NM];
+    for (int m = 0; m < NM; ++m) acc[m] = 0;
     for (int k = 0; k < 11; ++k) {
         const int xx = x + k - 5;
         if (xx < 0 || xx >= W) continue;
         const long long j = i + (k - 5);
-        const float wk = win.g[k];
+        const TO wk = win.g[k];
         if (MODE == 0) {
-            const float u = a[j], v = b[j];
+            const TO u = a[j], v = b[j];
             acc[0] += wk * u; acc[1] += wk * v; acc[2] += wk * (u * u); acc[3] += wk * (v * v); acc[4] += wk * (u * v);
         } else {
             for (int m = 0; m < NM; ++m) acc[m] += wk * a[m * CHW + j];
@@ -646,7 +649,7 @@ __device__ __forceinline__ void block_sum2(float& s0, float& s1, float (*sh)[NT]
 }
 
 // vertical pass + SSIM map; stores dS/dmu1, dS/dE[x^2], dS/dE[xy] per pixel and per-block partial sums (S, |x - y|)
-__global__ void ssim_vfwd_kernel(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ h5, long long C, int H, int W,
+__global__ void ssim_vfwd_kernel(const float* __restrict__ x, const float* __restrict__ y, const double* __restrict__ h5, long long C, int H, int W,
                                  Win win, float* __restrict__ gmaps, float* __restrict__ partial) {
     __shared__ float sh[2][NT];
     const long long CHW = C * H * W;
@@ -654,22 +657,23 @@ __global__ void ssim_vfwd_kernel(const float* __restrict__ x, const float* __res
     float S = 0.f, l1 = 0.f;
     if (i < CHW) {
         const int yy = (int)((i / W) % H);
-        float m[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+        double m[5] = {0., 0., 0., 0., 0.};
         for (int k = 0; k < 11; ++k) {
             const int r = yy + k - 5;
             if (r < 0 || r >= H) continue;
             const long long j = i + (long long)(k - 5) * W;
-            for (int q = 0; q < 5; ++q) m[q] += win.g[k] * h5[q * CHW + j];
+            for (int q = 0; q < 5; ++q) m[q] += (double)win.g[k] * h5[q * CHW + j];
         }
-        const float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;
-        const float mu1 = m[0], mu2 = m[1];
-        const float s11 = m[2] - mu1 * mu1, s22 = m[3] - mu2 * mu2, s12 = m[4] - mu1 * mu2;
-        const float A1 = 2.f * mu1 * mu2 + C1, A2 = 2.f * s12 + C2, B1 = mu1 * mu1 + mu2 * mu2 + C1, B2 = s11 + s22 + C2;
-        const float inv = 1.f / (B1 * B2);
-        S = A1 * A2 * inv;
-        gmaps[i] = (2.f * mu2 * A2 - 2.f * mu2 * A1) * inv - S * (2.f * mu1 / B1 - 2.f * mu1 / B2);
-        gmaps[CHW + i] = -S / B2;
-        gmaps[2 * CHW + i] = 2.f * A1 * inv;
+        const double C1 = 0.01 * 0.01, C2 = 0.03 * 0.03;
+        const double mu1 = m[0], mu2 = m[1];
+        const double s11 = m[2] - mu1 * mu1, s22 = m[3] - mu2 * mu2, s12 = m[4] - mu1 * mu2;
+        const double A1 = 2. * mu1 * mu2 + C1, A2 = 2. * s12 + C2, B1 = mu1 * mu1 + mu2 * mu2 + C1, B2 = s11 + s22 + C2;
+        const double inv = 1. / (B1 * B2);
+        const double Sd = A1 * A2 * inv;
+        S = (float)Sd;
+        gmaps[i] = (float)((2. * mu2 * A2 - 2. * mu2 * A1) * inv - Sd * (2. * mu1 / B1 - 2. * mu1 / B2));
+        gmaps[CHW + i] = (float)(-Sd / B2);
+        gmaps[2 * CHW + i] = (float)(2. * A1 * inv);
         l1 = fabsf(x[i] - y[i]);
     }
     block_sum2(S, l1, sh);
@@ -710,11 +714,16 @@ __global__ void ssim_vbwd_kernel(const float* __restrict__ x, const float* __res
 }
 
 Win ssim_window() {
-    float gf[11], sf = 0.f;
+    float gf[11];
+    double sd = 0.;
     for (int k = 0; k < 11; ++k) gf[k] = (float)exp(-0.5 * ((k - 5) / 1.5) * ((k - 5) / 1.5));
-    for (int k = 0; k < 11; ++k) sf += gf[k];
+    for (int k = 0; k < 11; ++k) sd += gf[k];
+    // fp32 normalisation, as the published loss builds its window.  The fp32 sum of the taps is the correctly rounded one (what a
+    // pairwise / vectorised fp32 sum of these 11 numbers gives; adding them left to right in fp32 lands one ulp below it, and a window
+    // whose sum is off by 7e-8 moves the variance of a flat region, c^2 S (1 - S), by ~1e-8 beside c2 = 9e-4)
+    const float sf = (float)sd;
     Win w;
-    for (int k = 0; k < 11; ++k) w.g[k] = gf[k] / sf;      // fp32 normalisation, as the published loss builds its window
+    for (int k = 0; k < 11; ++k) w.g[k] = gf[k] / sf;
     return w;
 }
 
@@ -797,10 +806,12 @@ extern "C" int v3d_gs_radix_sort_pairs(const uint64_t* keys_in, const uint32_t* 
         uint64_t* kd = to_out ? keys_out : ktmp;
         uint32_t* vd = to_out ? vals_out : vtmp;
         const int shift = pass * RS_BITS;
-        hipLaunchKernelGGL(radix_count_kernel, dim3(nb), dim3(NT), 0, ST, ks, (long long)n, shift, nb, counts);
+        // the last digit ends at bit nbits: key bits above it take no part, so keys that differ only there keep their input order
+        const unsigned dmask = (1u << (nbits - shift < RS_BITS ? nbits - shift : RS_BITS)) - 1u;
+        hipLaunchKernelGGL(radix_count_kernel, dim3(nb), dim3(NT), 0, ST, ks, (long long)n, shift, dmask, nb, counts);
         int rc = v3d_gs_scan(counts, nc, offs, swork, v3d_gs_scan_work_bytes(nc), stream);
         if (rc) return rc;
-        hipLaunchKernelGGL(radix_scatter_kernel, dim3(nb), dim3(NT), 0, ST, ks, vs, (long long)n, shift, nb, offs, kd, vd);
+        hipLaunchKernelGGL(radix_scatter_kernel, dim3(nb), dim3(NT), 0, ST, ks, vs, (long long)n, shift, dmask, nb, offs, kd, vd);
         ks = kd;
         vs = vd;
     }
@@ -865,7 +876,7 @@ extern "C" int v3d_gs_preprocess_bwd(const float* xyz, const float* scale_raw, c
 extern "C" int64_t v3d_gs_ssim_work_floats(int32_t C, int32_t H, int32_t W) {
     if (C <= 0 || H <= 0 || W <= 0) return -1;
     const long long chw = (long long)C * H * W;
-    return 8 * chw + 2 * (long long)nblk(chw);
+    return 13 * chw + 2 * (long long)nblk(chw);        // 5 fp64 moment maps, 3 gradient maps, per-block partial sums
 }
 
 extern "C" int v3d_gs_ssim_l1_fwd(const float* img, const float* gt, int32_t C, int32_t H, int32_t W, float lambda_dssim, float* work,
@@ -874,10 +885,11 @@ extern "C" int v3d_gs_ssim_l1_fwd(const float* img, const float* gt, int32_t C, 
     V3D_REQUIRE(work_floats >= v3d_gs_ssim_work_floats(C, H, W), "v3d_gs_ssim_l1_fwd: work buffer too small (v3d_gs_ssim_work_floats)");
     const long long chw = (long long)C * H * W, nb = nblk(chw);
     const Win win = ssim_window();
-    float* h5 = work;
-    float* gm = work + 5 * chw;
-    float* part = work + 8 * chw;
-    hipLaunchKernelGGL(ssim_hblur_kernel<0>, dim3(nb), dim3(NT), 0, ST, img, gt, (long long)C, (int)H, (int)W, win, h5);
+    V3D_REQUIRE(((uintptr_t)work & 7) == 0, "v3d_gs_ssim_l1_fwd: work must be 8-byte aligned");
+    double* h5 = (double*)work;
+    float* gm = work + 10 * chw;
+    float* part = work + 13 * chw;
+    hipLaunchKernelGGL((ssim_hblur_kernel<0, double>), dim3(nb), dim3(NT), 0, ST, img, gt, (long long)C, (int)H, (int)W, win, h5);
     hipLaunchKernelGGL(ssim_vfwd_kernel, dim3(nb), dim3(NT), 0, ST, img, gt, h5, (long long)C, (int)H, (int)W, win, gm, part);
     hipLaunchKernelGGL(ssim_final_kernel, dim3(1), dim3(NT), 0, ST, part, nb, chw, lambda_dssim, out3);
     return v3d_check_launch("v3d_gs_ssim_l1_fwd");
@@ -890,8 +902,8 @@ extern "C" int v3d_gs_ssim_l1_bwd(const float* img, const float* gt, int32_t C, 
     const long long chw = (long long)C * H * W, nb = nblk(chw);
     const Win win = ssim_window();
     float* h3 = work;               // (the forward's five blurred maps are no longer needed)
-    const float* gm = work + 5 * chw;
-    hipLaunchKernelGGL(ssim_hblur_kernel<1>, dim3(nb), dim3(NT), 0, ST, gm, nullptr, (long long)C, (int)H, (int)W, win, h3);
+    const float* gm = work + 10 * chw;
+    hipLaunchKernelGGL((ssim_hblur_kernel<1, float>), dim3(nb), dim3(NT), 0, ST, gm, (const float*)nullptr, (long long)C, (int)H, (int)W, win, h3);
     hipLaunchKernelGGL(ssim_vbwd_kernel, dim3(nb), dim3(NT), 0, ST, img, gt, h3, (long long)C, (int)H, (int)W, win, lambda_dssim, dloss, grad);
     return v3d_check_launch("v3d_gs_ssim_l1_bwd");
 }

@@ -125,6 +125,7 @@ def case_gemm(hip, emu, dev, *, M, N, K, mode=GEMM_LINEAR, geglu=False, bias=Tru
         st_2, out_2 = torch.zeros_like(st_h), torch.zeros_like(out_h)
         hip.gemm(GemmCall(out=out_2, gn_stats=st_2, gn_rps=gn_rps, gn_cpg=N // 32, **base))
         hip.gemm(GemmCall(out=out_h, gn_stats=st_h, gn_rps=gn_rps, gn_cpg=N // 32, **base))
+        _assert_launch_was_planned(hip, GemmCall(out=out_h, gn_stats=st_h, gn_rps=gn_rps, gn_cpg=N // 32, **base))
         assert torch.equal(out_2, out_h) and torch.equal(st_2, st_h), "two identical launches differ: the statistics epilogue is not deterministic"
         emu.gemm(GemmCall(out=out_e, gn_stats=st_e, gn_rps=gn_rps, gn_cpg=N // 32, **base))
         v = out_h.float().reshape(M // gn_rps, gn_rps, 32, N // 32)
@@ -139,6 +140,7 @@ def case_gemm(hip, emu, dev, *, M, N, K, mode=GEMM_LINEAR, geglu=False, bias=Tru
         return compare(out_h, out_e)
     sk0 = _sk_counter(hip, "v3d_debug_sk_launches") if expect_streamk is not None else 0
     hip.gemm(GemmCall(out=out_h, **base))
+    _assert_launch_was_planned(hip, GemmCall(out=out_h, **base))
     if expect_family is not None and getattr(hip, "name", "") == "hip" and not any(os.environ.get(k) for k in ("V3D_GEMM_IMPL", "V3D_GEMM_V6")):
         # the dispatcher's choice under the default policy (gemm.hip dispatch): 6 = two persistent 4-wave blocks per CU on 192 x 160 tiles
         fam = hip.last_gemm_launch()["family"]
@@ -412,6 +414,16 @@ def case_conv_gn(hip, emu, dev, *, N, C1, C2=0, conv=None, convt=None, add=False
     assert torch.equal(o_2, o_h), "two identical launches of the haloed kernel differ"
     _assert_no_sk_timeouts(hip)
     return compare(o_h, o_e)
+
+
+def _assert_launch_was_planned(hip, call):
+    """the launch the library just made for `call` is the one its planner reports for the same arguments (gemm.hip plan_gemm, the function
+    tests/test_gemm_plan.py pins without a GPU)"""
+    if getattr(hip, "name", "") != "hip":
+        return
+    plan, rec = hip.gemm_plan(call), hip.last_gemm_launch()
+    shared = ("family", "bm", "bn", "tiles", "splitk", "streamk_tail")
+    assert [plan[k] for k in shared] == [rec[k] for k in shared], f"planned {plan}, launched {rec}"
 
 
 def _sk_counter(hip, name):

@@ -571,14 +571,9 @@ __global__ __launch_bounds__(512, 2) void conv_halo_kernel(GP p, int ntiles) {
 // 0 = this launch is not one of the haloed kernels' shapes (the caller keeps its v3d_gemm path), else the HaloGeom variant id
 int v3d_conv_halo_variant(const V3dGemmParams& p, int mode) {
     auto al = [](const void* q, uintptr_t a) { return (reinterpret_cast<uintptr_t>(q) % a) == 0; };
-    if (p.N % 320 || p.K % 32 || p.K * 2 > 65536 || p.out_fp32 || p.split_n > 1) return 0;
-    if (!e4_ok(p, 96, 80)) return 0;                                // the kernels only carry the hand-managed epilogue
+    if (p.N % 320 || !v3d_k_steps_ok(p) || p.split_n > 1) return 0;
+    if (!e4_ok(p, 96, 80)) return 0;                                // the kernels only carry the hand-managed epilogue (bf16 output, aligned operands)
     if (p.A2 && (p.K1 <= 0 || p.K1 >= p.K || p.K1 % 32 || p.lda2 % 8 || !al(p.A2, 16))) return 0;
-    if (p.ldo % 8 || !al(p.out, 16)) return 0;
-    if (p.add && (!al(p.add, 16) || p.add_ld % 4)) return 0;
-    if (p.res1 && (!al(p.res1, 16) || p.ldr1 % 8)) return 0;
-    if (p.res2 && (!al(p.res2, 8) || p.ldr2 % 4)) return 0;
-    if (p.bias && !al(p.bias, 16)) return 0;
     if (p.gn_in && (p.gn_in_rps <= 0 || !al(p.gn_in, 16))) return 0;
     if (p.gn_in && !p.gn_in_silu) return 0;                         // the operand path applies GroupNorm + SiLU (every ResBlock half); a bare norm keeps the apply pass
     if (p.gn_stats && (80 % p.gn_cpg || p.gn_rps % 16)) return 0;
@@ -602,32 +597,24 @@ int v3d_conv_halo_variant(const V3dGemmParams& p, int mode) {
 }
 
 template <int HM, int W_>
-static int conv_halo_launch_t(const V3dGemmParams& p0, hipStream_t st) {
-    V3dGemmParams p = p0;
-    p.mt = (int)(p.M / 192);
-    p.nt = (int)(p.N / 320);
-    const int ntiles = p.mt * p.nt;
-    // (stream-K tail: the last round's tiles are cut at 32-channel chunks and shared out over all CUs; at least 4 chunks per piece and 2 chunks
-    // (18 / 6 steps) of idling removed)
-    const int grid = v3d_sk_plan(p, ntiles, (int)(p.K / 32), 4, 2, (size_t)192 * 320 * 4, (void*)st);
+static void conv_halo_launch_t(const V3dGemmParams& p, int grid, int ntiles, hipStream_t st) {
     const bool xf = p.gn_in != nullptr, gn = p.gn_stats != nullptr;
-    v3d_note_launch(5, 192, 320, ntiles, 1, p.sk_tail);
     if (xf && gn) hipLaunchKernelGGL((conv_halo_kernel<HM, W_, true, true>), dim3(grid), dim3(512), 0, st, p, ntiles);
     else if (xf) hipLaunchKernelGGL((conv_halo_kernel<HM, W_, true, false>), dim3(grid), dim3(512), 0, st, p, ntiles);
     else if (gn) hipLaunchKernelGGL((conv_halo_kernel<HM, W_, false, true>), dim3(grid), dim3(512), 0, st, p, ntiles);
     else hipLaunchKernelGGL((conv_halo_kernel<HM, W_, false, false>), dim3(grid), dim3(512), 0, st, p, ntiles);
-    return v3d_check_launch("v3d_gemm(haloed)");
 }
 
-int v3d_conv_halo_launch(const V3dGemmParams& p, int variant, void* stream) {
+int v3d_conv_halo_launch(const V3dGemmParams& p, int variant, int grid, int ntiles, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     switch (variant) {
-        case 1: return conv_halo_launch_t<HM_CONV, 64>(p, st);
-        case 2: return conv_halo_launch_t<HM_CONV, 32>(p, st);
-        case 3: return conv_halo_launch_t<HM_CONV, 16>(p, st);
-        case 4: return conv_halo_launch_t<HM_TEMP, 32>(p, st);
+        case 1: conv_halo_launch_t<HM_CONV, 64>(p, grid, ntiles, st); break;
+        case 2: conv_halo_launch_t<HM_CONV, 32>(p, grid, ntiles, st); break;
+        case 3: conv_halo_launch_t<HM_CONV, 16>(p, grid, ntiles, st); break;
+        case 4: conv_halo_launch_t<HM_TEMP, 32>(p, grid, ntiles, st); break;
+        default:
+            v3d_set_error("v3d_gemm(haloed): unknown variant %d", variant);
+            return V3D_ERR_ARG;
     }
-    v3d_set_error("v3d_gemm(haloed): unknown variant %d", variant);
-    return V3D_ERR_ARG;
+    return v3d_check_launch("v3d_gemm(haloed)");
 }
-

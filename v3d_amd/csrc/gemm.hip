@@ -5,14 +5,13 @@
 // v_mfma_f32_16x16x32_bf16 with the WEIGHT fragment as the A operand, so each lane ends up with 4 consecutive output
 // channels of one pixel (8-byte bf16 stores, float4 bias loads).
 //
-// Three main loops share the tap / row addressing (RowInfo) and the fused epilogue below:
-//   v3 (default wherever its tiles fill the CUs): persistent 8-wave blocks on 256 x 256 / 192 x 320 / 256 x 128 tiles, buffer-load
-//      LDS-DMA ring across tile boundaries, two wave groups per SIMD offset by half a step around ONE barrier per 32 k - see the
-//      block comment at gemm_kernel_v3.
-//   v2 (small-M levels, ragged edges, batched launches, split-K): one 128 x 128 / 256 x 128 / 256 x 64 tile per block, 2-3 blocks
-//      per CU; HBM/L2 -> LDS by global_load_lds_dwordx4 into an NS-deep ring of BK = 32 / 64 stages, counted s_waitcnt vmcnt(N) +
-//      one raw s_barrier per stage (never vmcnt(0) inside the loop); conv zero padding / M, N tails read a 64 KiB zero page.
-//   v1 (K % 32 != 0, V3D_GEMM_IMPL=1): register-staged double buffer with bounds-checked buffer loads.
+// The main loops (v1, v2, v3, v6 here, the LDS-haloed family in conv.hip) share the tap / row addressing (RowInfo) and the fused epilogue of
+// gemm_common.h; which one a call gets is decided by plan_gemm below - the table there lists every kernel, its tile and when it is chosen.
+//   v3 / v6: persistent blocks, buffer-load LDS-DMA ring across tile boundaries, two wave groups per SIMD offset by half a step around ONE
+//      barrier per 32 k - see the block comment at gemm_kernel_v3.
+//   v2: one tile per block, 2-3 blocks per CU; HBM/L2 -> LDS by global_load_lds_dwordx4 into an NS-deep ring of BK = 32 / 64 stages, counted
+//      s_waitcnt vmcnt(N) + one raw s_barrier per stage (never vmcnt(0) inside the loop); conv zero padding / M, N tails read a 64 KiB zero page.
+//   v1: register-staged double buffer with bounds-checked buffer loads.
 // LDS rows are 64 B (128 B for BK = 64); the 16-byte chunk position of a row is XOR-swizzled on the per-lane SOURCE address (the
 // LDS-DMA destination is lane-linear) so every ds_read_b128 lane group hits 16 distinct 16-byte slots.
 #include <stdlib.h>
@@ -735,10 +734,10 @@ float* splitk_workspace(size_t floats, hipStream_t st) {
     return s.ptr;
 }
 
-// ---- launch record (tests / tools / bench.py --shard-sim): what the last v3d_gemm of this thread actually launched --------------------------------
-// family (1 = v1, 2 = v2, 3 = v3 persistent, 5 = LDS-haloed (conv.hip)), tile, tile count, co-resident blocks per CU (the runtime's occupancy
-// answer for that kernel), split-K ways, stream-K tail.  Read back through v3d_debug_last_gemm_launch.
+// ---- launch record (tests / tools / bench.py --shard-sim): what the last v3d_gemm of this thread launched, written once per call from its plan:
+// family, tile, tile count, co-resident blocks per CU (the runtime's occupancy answer for that kernel), split-K ways, stream-K tail.
 thread_local V3dLaunchInfo g_last_launch = {0, 0, 0, 0, 0, 0, 0};
+long long g_gn_epilogue_launches = 0;      // (tests: how many launches of this process gathered GroupNorm statistics in a v3 <GN> epilogue)
 template <typename K>
 int v3d_occupancy(K kernel, int threads) {
     int n = 0;
@@ -748,277 +747,205 @@ int v3d_occupancy(K kernel, int threads) {
     }
     return n;
 }
-void v3d_note_launch_splitk(int ways) { g_last_launch.splitk = ways; }
-#define V3D_LAUNCH(FAM, BM_, BN_, TILES, KERNEL, GRID, THREADS, ST, ...)                               \
-    do {                                                                                             \
-        static const int occ_ = v3d_occupancy(KERNEL, THREADS);                                      \
-        v3d_note_launch(FAM, BM_, BN_, (long long)(TILES), occ_, 0);                                 \
-        hipLaunchKernelGGL(KERNEL, GRID, dim3(THREADS), 0, ST, __VA_ARGS__);                         \
+#define V3D_LAUNCH(KERNEL, ...)                                                                                          \
+    do {                                                                                                                 \
+        static const int occ_ = v3d_occupancy(KERNEL, pl.threads);                                                       \
+        occ = occ_;                                                                                                      \
+        hipLaunchKernelGGL(KERNEL, dim3(pl.grid_x, pl.grid_y, 1), dim3(pl.threads), 0, st, __VA_ARGS__);                 \
     } while (0)
 
-int impl_choice() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("V3D_GEMM_IMPL");
-        v = e ? atoi(e) : 0;   // 0 = heuristic, 1 = v1 only, 2 = v1/v2 only, 3 = v3 wherever it is legal
-    }
-    return v;
-}
-int splitk_choice() {
-    static int v = -2;
-    if (v == -2) {
-        const char* e = getenv("V3D_GEMM_SPLITK");   // 0 = never, N = force N-way where legal, unset = heuristic
-        v = e ? atoi(e) : -1;
-    }
-    return v;
-}
-
-template <int BM, int BN, int MODE, bool GEGLU>
-int launch(const GP& p0, int batch, hipStream_t st) {
-    GP p = p0;
-    p.mt = (int)((p.M + BM - 1) / BM);
-    p.nt = (int)((p.N + BN - 1) / BN);
-    dim3 grid((unsigned)(p.mt * p.nt), (unsigned)batch, 1);
-    // split-K: the 8x8 level has 180 tiles of 128 x 128 for 256 CUs and contractions of 160-720 steps, so a launch lasts as long as
-    // ONE tile (conv 8x8 1280->1280: 153 us, 444 TF/s).  Splitting the flat (tap, k) range 2-4 ways fills the CUs; the partial sums
-    // meet in an fp32 workspace (atomics) and a small finalize kernel applies the epilogue.
-    if constexpr (!GEGLU && BM == 128) {
-        const long long tiles = (long long)p.mt * p.nt, cus = v3d_num_cus();
-        const long long steps = (long long)ntaps<MODE>() * (p.K / 32);
-        int want = splitk_choice();
-        if (want < 0) want = (tiles * 4 <= cus * 3 && steps >= 96) ? (int)((3 * cus + tiles - 1) / tiles) : 1;   // 8x8 conv: 546 / 693 / 617 / 699 TF/s at 1 / 2 / 3 / 4
-        if (want > 4) want = 4;
-        if (want > steps / 32) want = (int)(steps / 32);
-        if (want > 1 && batch == 1 && impl_choice() != 1 && p.K % 64 == 0 && p.K * 2 <= 65536 && p.N % 4 == 0 && p.ldo % 4 == 0 &&
-            (!p.res1 || (p.ldr1 % 4 == 0 && reinterpret_cast<uintptr_t>(p.res1) % 8 == 0)) &&
-            (!p.res2 || (p.ldr2 % 4 == 0 && reinterpret_cast<uintptr_t>(p.res2) % 8 == 0)) &&
-            (!p.add || (p.add_ld % 4 == 0 && reinterpret_cast<uintptr_t>(p.add) % 16 == 0)) &&
-            reinterpret_cast<uintptr_t>(p.out) % 16 == 0) {
-            float* ws = splitk_workspace((size_t)want * (size_t)p.M * (size_t)p.N, st);
-            if (ws) {
-                GP q = p;                 // the split launch: plain fp32 partial sums, slab `split`
-                q.split_n = want;
-                q.out = ws; q.out_fp32 = 1; q.ldo = p.N; q.sO = p.M * p.N; q.sA = 0; q.sW = 0;
-                q.bias = nullptr; q.add = nullptr; q.res1 = nullptr; q.res2 = nullptr; q.coef = nullptr;
-                q.c_acc = 1.f; q.c_res1 = 0.f; q.c_res2 = 0.f;
-                dim3 g2((unsigned)(p.mt * p.nt), (unsigned)want, 1);
-                V3D_LAUNCH(2, BM, BN, (long long)g2.x * g2.y, (gemm_kernel_v2<BM, BN, 2, 2, 2, 2, MODE, GEGLU>), g2, 256, st, q);
-                p.split_n = want;
-                p.ws = ws;
-                const long long n4 = p.M * (p.N / 4);
-                v3d_note_launch_splitk(want);
-                hipLaunchKernelGGL(splitk_finalize_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, p);
-                return v3d_check_launch("v3d_gemm(split-K)");
-            }
-        }
-    }
-    if (impl_choice() == 1 || p.K % 32 != 0 || p.K * 2 > 65536) {   // (impl 0 / 2 / 3 all land here for v2-class shapes)
-        // v1 also serves ragged contractions (K % 32 != 0: the 8-channel input conv, odd test shapes)
-        V3D_LAUNCH(1, BM, BN, (long long)grid.x * grid.y, (gemm_kernel_v1<BM, BN, MODE, GEGLU>), grid, 256, st, p);
-        return v3d_check_launch("v3d_gemm");
-    }
-    if constexpr (BN == 64) {
-        // 64-wide N tiles (N = 320 and friends): a 256 x 64 tile with the 4 waves stacked along M (wave tile 64 x 64) doubles the MFMAs per
-        // barrier and halves the weight re-reads (lin_L0_320x320 433 -> 487, convt_L0_320 568 -> 734 TF/s); BK 64 x 2 stages, BK 32 x 3 when K % 64 != 0
-        p.mt = (int)((p.M + 255) / 256);
-        const dim3 g2((unsigned)(p.mt * p.nt), (unsigned)batch, 1);
-        if (p.K % 64 == 0)
-            V3D_LAUNCH(2, 256, 64, (long long)g2.x * g2.y, (gemm_kernel_v2<256, 64, 4, 1, 2, 2, MODE, GEGLU>), g2, 256, st, p);
-        else
-            V3D_LAUNCH(2, 256, 64, (long long)g2.x * g2.y, (gemm_kernel_v2<256, 64, 4, 1, 3, 1, MODE, GEGLU>), g2, 256, st, p);
-    } else if (((GEGLU && p.K >= 640) || (MODE == V3D_GEMM_CONV3X3 && p.K <= 128)) && p.M >= 4096) {
-        // wide GEGLU projections at K >= 640 and the 128-channel VAE convs: 256 x 128 tile on 4 waves (wave tile 128 x 64, 32 MFMAs per barrier,
-        // 25 % fewer LDS-fill bytes per flop), BK 32 x 3 stages: 72 KiB -> 2 blocks / CU (lin_L1_ff1_geglu 662 -> 779, lin_L2_ff1_geglu 708 -> 865 TF/s)
-        p.mt = (int)((p.M + 255) / 256);
-        const dim3 g2((unsigned)(p.mt * p.nt), (unsigned)batch, 1);
-        V3D_LAUNCH(2, 256, 128, (long long)g2.x * g2.y, (gemm_kernel_v2<256, 128, 2, 2, 3, 1, MODE, GEGLU>), g2, 256, st, p);
-    } else if ((long long)ntaps<MODE>() * ((p.K + 31) / 32) <= 40) {
-        // measured on MI355X (profiles/r01_gemm_sweep.txt): short contractions (<= 40 stages of 32: every K <= 1280 linear, the 128-channel
-        // VAE convs) are bound by per-tile fill/drain bubbles -> more co-resident blocks: BK 32 x 3 stages, 48 KiB LDS, 3 blocks / CU
-        V3D_LAUNCH(2, BM, BN, (long long)grid.x * grid.y, (gemm_kernel_v2<BM, BN, 2, 2, 3, 1, MODE, GEGLU>), grid, 256, st, p);
-    } else if (p.K % 64 == 0) {
-        // long contractions prefer fewer barriers per MFMA: BK 64 x 2 stages (one in flight)
-        V3D_LAUNCH(2, BM, BN, (long long)grid.x * grid.y, (gemm_kernel_v2<BM, BN, 2, 2, 2, 2, MODE, GEGLU>), grid, 256, st, p);
-    } else {
-        V3D_LAUNCH(2, BM, BN, (long long)grid.x * grid.y, (gemm_kernel_v2<BM, BN, 2, 2, 4, 1, MODE, GEGLU>), grid, 256, st, p);   // BK 32 x 4 stages
-    }
-    return v3d_check_launch("v3d_gemm");
+// ---- policy: the A/B knobs, read from the environment once ------------------------------------------------------------------------------------------
+struct GemmPolicy {
+    int impl;      // V3D_GEMM_IMPL: 0 = heuristic, 1 = v1 only, 2 = v1/v2 only, 3 = v3 wherever it is legal
+    int splitk;    // V3D_GEMM_SPLITK: 0 = never, N = force N-way where legal, -1 (unset) = heuristic
+    int v3s;       // V3D_GEMM_V3S: 0 disables the two-blocks-per-CU GEGLU kernel, 1 = K < 640 only, 2 = every GEGLU projection.  In isolation it ties with the
+                   // 256 x 256 kernel (402 vs 396 us); inside the sampler it is +0.9 % end to end (same-box A/B), 2 another +0.35 %
+    int v6;        // V3D_GEMM_V6: 0 = never, 1 = where v3's tiles quantise badly (the rule in plan_gemm), 2 = every legal launch
+    int streamk;   // V3D_STREAMK: 0 = classic tile assignment everywhere
+};
+const GemmPolicy& env_policy() {
+    static const GemmPolicy pol = [] {
+        auto rd = [](const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; };
+        return GemmPolicy{rd("V3D_GEMM_IMPL", 0), rd("V3D_GEMM_SPLITK", -1), rd("V3D_GEMM_V3S", 2), rd("V3D_GEMM_V6", 1), rd("V3D_STREAMK", 1)};
+    }();
+    return pol;
 }
 
+// ---- plan: which kernel a call gets -----------------------------------------------------------------------------------------------------------------
+//   id                 family  tile (BM x BN)  waves / blocks per CU      chosen when
+//   K_V1                  1    128 x 64|128    4 / 2                      K % 32 != 0 (the 8-channel input conv, odd test shapes), K > 32768, V3D_GEMM_IMPL=1
+//   K_V2_128_3x32         2    128 x 128       4 / 3, BK 32 x 3 stages    v2 launches (small M, ragged edges, batched) of <= 40 stages of 32
+//   K_V2_128_2x64         2    128 x 128       4 / 2, BK 64 x 2           ... longer contractions with K % 64 == 0
+//   K_V2_128_4x32         2    128 x 128       4 / 2, BK 32 x 4           ... longer contractions with K % 64 != 0
+//   K_V2_256x64_2x64/3x32 2    256 x 64        4 / 2, BK 64 x 2 | 32 x 3  v2 launches where 64-wide N tiles waste less than 128-wide ones (N = 320 and friends)
+//   K_V2_256x128          2    256 x 128       4 / 2, BK 32 x 3           v2 launches of GEGLU projections at K >= 640 / 3 x 3 convs at K <= 128 with M >= 4096
+//   K_SPLITK              2    128 x 64|128    4 / 2, BK 64 x 2 + finalize  v2 launches whose tiles cover <= 3/4 of the CUs with >= 96 steps (the 8 x 8 level)
+//   K_V3_256              3    256 x 256       8 / 1 persistent           default wherever v3's tiles fill the CUs about as well as v2's would
+//   K_V3_256_GEGLU42      3    256 x 256       8 / 1, waves 4 x 2         ... GEGLU projections at K < 640 that the two-per-CU kernel does not take
+//   K_V3_256_GN           3    256 x 256       8 / 1, statistics epilogue ... with gn_stats (whole groups per wave column, enough slots)
+//   K_V3_192x320 (_GN)    3    192 x 320       8 / 1 (statistics epilogue) ... the N % 320 == 0 family
+//   K_V3_256x128_GEGLU    3    256 x 128       8 / 2                      GEGLU projections with >= 2 tiles per CU (V3D_GEMM_V3S)
+//   K_V6                  6    192 x 160       4 / 2 persistent           linear / temporal launches where v3's tiles leave a partial round (rule below)
+//   K_HALO1 .. 4          5    192 x 320       8 / 1 persistent, stream-K tail   gn_in_table: 3 x 3 conv at W = 64 / 32 / 16, temporal conv (conv.hip v3d_conv_halo_variant)
+enum GemmKernel {
+    K_V1, K_V2_128_2x64, K_V2_128_3x32, K_V2_128_4x32, K_V2_256x64_2x64, K_V2_256x64_3x32, K_V2_256x128, K_SPLITK,
+    K_V3_256, K_V3_256_GEGLU42, K_V3_256_GN, K_V3_192x320, K_V3_192x320_GN, K_V3_256x128_GEGLU, K_V6, K_HALO1, K_HALO2, K_HALO3, K_HALO4,
+    K_COUNT, K_NONE = -1      // K_NONE: gn_in_table on a shape the haloed kernels do not take
+};
+struct GemmPlan {
+    int kernel, family, bm, bn, mt, nt;
+    long long tiles;                           // as the launch record reports them (x batch, x split-K ways)
+    unsigned grid_x, grid_y;
+    int threads, group_m, splitk;              // splitk: ways, 0 = not split
+    int sk_tail, sk_full, sk_units;            // stream-K tail (0 = classic), see V3dGemmParams
+    size_t sk_slot_bytes;
+    bool gn_in_epilogue;                       // the launch gathers gn_stats itself (else v3d_gemm runs the stand-alone kernel)
+    int mode;
+    bool geglu;
+};
+
+// operands of the 4-wide epilogue accesses (8-byte bf16 / 16-byte fp32 vectors): shared by the v3 tile contract and the split-K finalize
+// (bias: 16-byte alignment is an argument check of fill_params)
+bool vec4_operands(const GP& p) {
+    auto al = [](const void* q, uintptr_t a) { return (reinterpret_cast<uintptr_t>(q) % a) == 0; };
+    return al(p.out, 16) && (!p.add || (al(p.add, 16) && p.add_ld % 4 == 0)) && (!p.res1 || (al(p.res1, 8) && p.ldr1 % 4 == 0)) &&
+           (!p.res2 || (al(p.res2, 8) && p.ldr2 % 4 == 0));
+}
 // the v3 kernels only carry the branch-free epilogue: every wave tile (wm x wn) must be fully inside or fully outside the
 // output and all vector-access alignment conditions of the fast path must hold
-bool v3_ok(const GP& p, int wm, int wn) {
-    auto al = [](const void* q, uintptr_t a) { return (reinterpret_cast<uintptr_t>(q) % a) == 0; };
-    if (p.M % wm || p.N % wn) return false;
-    if (p.out_fp32 ? (p.ldo % 4 != 0 || !al(p.out, 16)) : (p.ldo % 8 != 0 || !al(p.out, 16))) return false;
-    if (p.add && (!al(p.add, 16) || p.add_ld % 4)) return false;
-    if (p.res1 && (!al(p.res1, 8) || p.ldr1 % 4)) return false;
-    if (p.res2 && (!al(p.res2, 8) || p.ldr2 % 4)) return false;
-    if (p.bias && !al(p.bias, 16)) return false;
-    return true;
-}
+bool v3_ok(const GP& p, int wm, int wn) { return p.M % wm == 0 && p.N % wn == 0 && p.ldo % (p.out_fp32 ? 4 : 8) == 0 && vec4_operands(p); }
 
-int v3s_choice() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("V3D_GEMM_V3S");   // 0 disables the two-blocks-per-CU GEGLU variant.  In isolation it ties with the
-        v = e ? atoi(e) : 2;                      // 256 x 256 kernel (402 vs 396 us); inside the sampler it is +0.9 % end to end (same-box A/B);
-                                                  // 1 = K < 640 only, 2 = every GEGLU projection (+0.35 % more)
+// pure: no HIP call, no environment, no state.  `p` = checked arguments (fill_params).
+GemmPlan plan_gemm(const GP& p, int mode, bool geglu, int batch, int cus, const GemmPolicy& pol) {
+    GemmPlan pl = {};
+    pl.kernel = K_NONE;
+    pl.group_m = -1;                           // tile walk: the heuristic of tile_coords (v6 sets its own)
+    pl.mode = mode;
+    pl.geglu = geglu;
+    auto cdiv = [](long long a, long long b) { return (a + b - 1) / b; };
+    auto tile = [&](int kernel, int family, int bm, int bn, int threads) {
+        pl.kernel = kernel; pl.family = family; pl.bm = bm; pl.bn = bn; pl.threads = threads;
+        pl.mt = (int)cdiv(p.M, bm); pl.nt = (int)cdiv(p.N, bn);
+        pl.tiles = (long long)pl.mt * pl.nt;
+    };
+    auto persistent = [&](long long slots) { pl.grid_x = (unsigned)(pl.tiles < slots ? pl.tiles : slots); pl.grid_y = 1; return pl; };
+    // a launch of t tiles on G block slots idles (ceil(t / G) G - t) / G of its last round, and the N tail of its last tile column
+    auto fill = [&](long long bm, long long bn, long long slots) {
+        const long long t = cdiv(p.M, bm) * cdiv(p.N, bn);
+        return (double)t / (double)(cdiv(t, slots) * slots) * ((double)p.N / (double)(cdiv(p.N, bn) * bn));
+    };
+    const int taps = mode == V3D_GEMM_LINEAR ? 1 : (mode == V3D_GEMM_CONV3X3 ? 9 : 3);
+    const bool dma_ok = v3d_k_steps_ok(p);     // the LDS-DMA kernels: whole 32-k steps, rows within reach of the zero page
+
+    if (p.gn_in) {   // GroupNorm (+SiLU) of the input in the operand path: only the LDS-haloed kernels (their epilogue gathers gn_stats itself)
+        const int halo = v3d_conv_halo_variant(p, mode);
+        if (!halo) return pl;
+        tile(K_HALO1 + halo - 1, 5, 192, 320, 512);
+        pl.gn_in_epilogue = p.gn_stats != nullptr;
+        // stream-K tail: the last round's tiles are cut at 32-channel chunks and shared out over all CUs.  Worth it when the partial round leaves >= 1/8 of
+        // the chip idle, every block still gets a piece of >= 4 chunks, and the idle time it removes ((G - R) / G of a tile) is >= 2 chunks (18 / 6 steps):
+        // the hand-off costs 10-15 us per owner (publish 245 KB write-through, flag, read back).
+        const int G = cus, R = (int)(pl.tiles % G), units = (int)(p.K / 32);
+        if (pol.streamk && R != 0 && (G - R) * 8 >= G && (long long)R * units / G >= 4 && (long long)(G - R) * units / G >= 2) {
+            pl.sk_tail = R; pl.sk_full = (int)(pl.tiles / G); pl.sk_slot_bytes = (size_t)192 * 320 * 4;
+            pl.grid_x = (unsigned)G; pl.grid_y = 1;
+        } else {
+            persistent(G);
+        }
+        pl.sk_units = units;
+        return pl;
     }
-    return v;
-}
 
-// set by launch_v3 when the launch it made gathers GroupNorm statistics in its epilogue (else v3d_gemm runs the stand-alone kernel)
-thread_local bool g_gn_in_epilogue = false;
-long long g_gn_epilogue_launches = 0;      // (tests: how many launches of this process gathered the statistics in their epilogue)
-
-template <int MODE, bool GEGLU>
-int launch_v3(const GP& p0, hipStream_t st, int variant) {
-    GP p = p0;
-    const int bm = variant == 1 ? 192 : 256, bn = variant == 1 ? 320 : (variant == 2 ? 128 : 256);
-    p.mt = (int)((p.M + bm - 1) / bm);
-    p.nt = (int)((p.N + bn - 1) / bn);
-    const int ntiles = p.mt * p.nt;
-    const int grid = ntiles < v3d_num_cus() ? ntiles : v3d_num_cus();
-    if constexpr (GEGLU && MODE == V3D_GEMM_LINEAR) {
-        if (variant == 2) {   // epilogue-bound GEGLU projections (K = 320): 256 x 128 tile, two blocks per CU
-            const int g2 = ntiles < 2 * v3d_num_cus() ? ntiles : 2 * v3d_num_cus();
-            V3D_LAUNCH(3, 256, 128, ntiles, (gemm_kernel_v3<256, 128, 4, 2, MODE, GEGLU, 1, 3, 0>), dim3(g2), 512, st, p, ntiles);
-            return v3d_check_launch("v3d_gemm");
+    // Tile quantisation of the persistent kernels (round 6).  The 32 x 32 and 16 x 16 levels of the U-Net sit at 1.4 - 2.25 rounds of v3 tiles.  gemm_kernel_v6's
+    // 192 x 160 tiles on 512 slots halve the granule: measured (profiles/r06_v6_ab.txt) -9 ... -14 % on the M = 9216 projections (N = 2560 / 3840) and the
+    // N = K = 640 linears, -5 % on the 32 x 32 temporal convolution, a tie where v3's tiles fill >= 0.9 of their rounds or K = 2560 (v2 is as good there),
+    // +1 ... 6 % where v3 runs whole rounds (N = 320 at 64 x 64, M = 36864 x N = 1280) - those stay where they were.  Also measured and dropped (same record): a SPLIT
+    // launch (v3 on the rows that make whole rounds, the tail rows as a second launch on 192 x 160 / 96 x 160 tiles: +5 ... 8 % slower than either single launch - the
+    // second launch's ramp costs more than the idle half round), 192 x 128 tiles for N = 1280 at M = 9216 (480 tiles on 512 slots: +4 ... 18 % slower than v3's 192
+    // tiles at 0.75 of a round), and 96 x 160 tiles for launches whose v3 tiles cover half the CUs or fewer (the 8 x 8 level, the 4 - 6-image ranks of a frame
+    // shard: +-3 %, and 1.6x slower than split-K at K = 5120).
+    const bool n320 = !geglu && p.N % 320 == 0;                 // v3's 192 x 320 tile (wave tile 96 x 80; 147456 rows = 768 tiles = 3 per CU)
+    const int bm3 = n320 ? 192 : 256, bn3 = n320 ? 320 : 256;
+    const double fill3 = fill(bm3, bn3, cus);
+    if (pol.v6 && pol.impl == 0 && mode != V3D_GEMM_CONV3X3 && !geglu && batch == 1 && dma_ok && p.M % 192 == 0 && p.N % 160 == 0 && !p.gn_stats && e4_ok(p, 96, 80)) {
+        const long long t6 = (p.M / 192) * (p.N / 160), slots = 2ll * cus;
+        if (t6 >= slots && (pol.v6 >= 2 || (p.K <= 1280 && fill3 < 0.9 && fill(192, 160, slots) >= fill3))) {
+            tile(K_V6, 6, 192, 160, 256);
+            pl.group_m = 0;      // row-major walk: the N-tiles of a row tile are consecutive ids -> blocks 8 apart on one XCD share its activation rows in L2
+            return persistent(slots);
         }
     }
-    if constexpr (!GEGLU) {
-        if (variant == 1) {   // the N = 320 family: 192 x 320 tile, wave tile 96 x 80 (147456 rows = 768 tiles = 3 per CU)
-            // statistics epilogue: every writer (wave tile x statistics group) stores into its own slot - needs whole groups per wave column
-            // and gn_rps / (wave tile rows) + 2 slots
-            if (p.gn_stats && 80 % p.gn_cpg == 0 && p.gn_nslots >= p.gn_rps / 96 + 2) {
-                g_gn_in_epilogue = true;
-                ++g_gn_epilogue_launches;
-                V3D_LAUNCH(3, 192, 320, ntiles, (gemm_kernel_v3<192, 320, 2, 4, MODE, GEGLU, 1, 4, 16, true>), dim3(grid), 512, st, p, ntiles);
-            } else {
-                V3D_LAUNCH(3, 192, 320, ntiles, (gemm_kernel_v3<192, 320, 2, 4, MODE, GEGLU, 1>), dim3(grid), 512, st, p, ntiles);
-            }
-            return v3d_check_launch("v3d_gemm");
-        }
-        if (p.gn_stats && variant == 0 && 64 % p.gn_cpg == 0 && p.gn_nslots >= p.gn_rps / 128 + 2) {
-            g_gn_in_epilogue = true;
-            ++g_gn_epilogue_launches;
-            V3D_LAUNCH(3, 256, 256, ntiles, (gemm_kernel_v3<256, 256, 2, 4, MODE, GEGLU, 1, 4, 16, true>), dim3(grid), 512, st, p, ntiles);
-            return v3d_check_launch("v3d_gemm");
-        }
-    }
-    if constexpr (GEGLU) {
-        // GEGLU halves the output width: with waves laid out 4 (M) x 2 (N) a wave owns 128 weight rows = 64 output channels = whole
-        // 128-byte lines of every output row (the 2 x 4 layout wrote 64-byte half lines from two different waves)
-        // measured (tools/gemm_floor.py, M = 147456, N = 2560): K = 320: 396 us vs 416 us (2 x 4) vs 402 us (two 256 x 128 blocks
-        // per CU) vs 421 us (v2); at K >= 640 the 2 x 4 layout with 32-row chunks is ahead again (tools/gemm_sweep.py)
-        if (p.K < 640) {
-            V3D_LAUNCH(3, 256, 256, ntiles, (gemm_kernel_v3<256, 256, 4, 2, MODE, GEGLU, 1>), dim3(grid), 512, st, p, ntiles);
-            return v3d_check_launch("v3d_gemm");
-        }
-    }
-    // epilogue chunk: 2 row fragments for GEGLU (its staged rows are half as wide), 1 otherwise (LDS budget next to the ring)
-    V3D_LAUNCH(3, 256, 256, ntiles, (gemm_kernel_v3<256, 256, 2, 4, MODE, GEGLU, GEGLU ? 2 : 1>), dim3(grid), 512, st, p, ntiles);
-    return v3d_check_launch("v3d_gemm");
-}
-
-// v6 (two persistent 4-wave blocks per CU).  V3D_GEMM_V6: 0 = never, 1 = where v3's tiles quantise badly (the rule in dispatch), 2 = every legal launch (A/B knob)
-int v6_choice() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("V3D_GEMM_V6");
-        v = e ? atoi(e) : 1;
-    }
-    return v;
-}
-template <int MODE>
-int launch_v6(const GP& p0, hipStream_t st) {
-    GP p = p0;
-    p.mt = (int)(p.M / 192);
-    p.nt = (int)(p.N / 160);
-    p.group_m = 0;                       // row-major walk: the N-tiles of a row tile are consecutive ids -> blocks 8 apart on one XCD share its activation rows in L2
-    const int ntiles = p.mt * p.nt;
-    const int grid = ntiles < 2 * v3d_num_cus() ? ntiles : 2 * v3d_num_cus();
-    V3D_LAUNCH(6, 192, 160, ntiles, (gemm_kernel_v6<192, 160, 3, MODE>), dim3(grid), 256, st, p, ntiles);
-    return v3d_check_launch("v3d_gemm(v6)");
-}
-
-// Tile quantisation of the persistent kernels (round 6).  A launch of t tiles on G block slots idles (ceil(t / G) G - t) / G of its last round; the
-// 32 x 32 and 16 x 16 levels of the U-Net sit at 1.4 - 2.25 rounds of v3 tiles.  gemm_kernel_v6's 192 x 160 tiles on 512 slots halve the granule:
-// measured (profiles/r06_v6_ab.txt) -9 ... -14 % on the M = 9216 projections (N = 2560 / 3840) and the N = K = 640 linears, -5 % on the 32 x 32 temporal
-// convolution, a tie where v3's tiles fill >= 0.9 of their rounds or K = 2560 (v2 is as good there), +1 ... 6 % where v3 runs whole rounds (N = 320 at
-// 64 x 64, M = 36864 x N = 1280) - those stay where they were.  Also measured and dropped (same record): a SPLIT launch (v3 on the rows that make whole rounds,
-// the tail rows as a second launch on 192 x 160 / 96 x 160 tiles: +5 ... 8 % slower than either single launch - the second launch's ramp costs more than the
-// idle half round), 192 x 128 tiles for N = 1280 at M = 9216 (480 tiles on 512 slots: +4 ... 18 % slower than v3's 192 tiles at 0.75 of a round), and 96 x 160 tiles for
-// launches whose v3 tiles cover half the CUs or fewer (the 8 x 8 level, the 4 - 6-image ranks of a frame shard: +-3 %, and 1.6x slower than split-K at K = 5120).
-// returns -1 when the rule does not apply (the caller keeps its v3 / v2 path).  V3D_GEMM_V6: 0 = never, 1 = the rule (default), 2 = every legal launch (A/B knob)
-template <int MODE>
-int try_v6(const GP& p, hipStream_t st) {
-    const int v6 = v6_choice();
-    if (!v6 || impl_choice() != 0 || p.K % 32 || p.K * 2 > 65536 || p.M % 192 || p.N % 160 || p.gn_stats || !e4_ok(p, 96, 80)) return -1;
-    const long long cus = v3d_num_cus(), slots = 2 * cus;
-    const bool v1 = p.N % 320 == 0;
-    const long long bm = v1 ? 192 : 256, bn = v1 ? 320 : 256;
-    const long long t3 = ((p.M + bm - 1) / bm) * ((p.N + bn - 1) / bn), t6 = (p.M / 192) * (p.N / 160);
-    const double fill3 = (double)t3 / (double)(((t3 + cus - 1) / cus) * cus) * ((double)p.N / (double)(((p.N + bn - 1) / bn) * bn));
-    const double fill6 = (double)t6 / (double)(((t6 + slots - 1) / slots) * slots);
-    if (t6 >= slots && (v6 >= 2 || (p.K <= 1280 && fill3 < 0.9 && fill6 >= fill3))) return launch_v6<MODE>(p, st);
-    return -1;
-}
-
-template <int MODE, bool GEGLU>
-int dispatch(const GP& p, int batch, hipStream_t st) {
-    if constexpr ((MODE == V3D_GEMM_LINEAR || MODE == V3D_GEMM_CONVT3) && !GEGLU) {
-        if (batch == 1) {
-            const int rc = try_v6<MODE>(p, st);
-            if (rc >= 0) return rc;
-        }
-    }
-    // v3 (persistent big tiles) unless forced off (V3D_GEMM_IMPL=1/2), forced on (=3), or the tile count fills the CUs badly
-    if (impl_choice() != 1 && impl_choice() != 2 && batch == 1 && p.K % 32 == 0 && p.K * 2 <= 65536 && p.N >= 256) {
-        const int variant = (!GEGLU && p.N % 320 == 0) ? 1 : 0;
-        const long long bm = variant ? 192 : 256, bn = variant ? 320 : 256;
-        const long long nt3 = ((p.M + bm - 1) / bm) * ((p.N + bn - 1) / bn), cus = v3d_num_cus();
-        const double fill3 = (double)nt3 / (double)(((nt3 + cus - 1) / cus) * cus) * ((double)p.N / (double)(((p.N + bn - 1) / bn) * bn));
-        // v2 reference point: 128 x 128 (or x 64) tiles, 2 blocks per CU
-        const long long w128 = ((p.N + 127) / 128) * 128, w64 = ((p.N + 63) / 64) * 64, wv2 = w64 < w128 ? w64 : w128;
-        const long long nt2 = ((p.M + 127) / 128) * (wv2 / (w64 < w128 ? 64 : 128));
-        const double fill2 = (double)nt2 / (double)(((nt2 + 2 * cus - 1) / (2 * cus)) * 2 * cus) * ((double)p.N / (double)wv2);
-        // measured (profiles/r01f_op_times_v3.txt): v3 wins wherever its tiles fill the CUs about as well as v2's do
-        if (GEGLU && (p.K < 640 || v3s_choice() >= 2) && v3s_choice() && v3_ok(p, 64, 64) && ((p.M + 255) / 256) * ((p.N + 127) / 128) >= 2 * cus)
-            return launch_v3<MODE, GEGLU>(p, st, 2);
-        const bool want = impl_choice() == 3 || fill3 >= 0.9 * fill2;
-        // (non-GEGLU v3 kernels only carry the hand-managed epilogue: its operand contract on top of the tile-shape one)
-        const bool eok = GEGLU || (variant ? e4_ok(p, 96, 80) : e4_ok(p, 128, 64));
-        if (want && eok && (variant ? v3_ok(p, 96, 80) : v3_ok(p, 128, 128))) {
-            return launch_v3<MODE, GEGLU>(p, st, variant);
-        }
-    }
-    // N tile: 128 unless a 64-wide tile wastes less (e.g. N = 320: 5 x 64 exact vs 3 x 128 = 17 % padding)
-    const long long w128 = ((p.N + 127) / 128) * 128, w64 = ((p.N + 63) / 64) * 64;
+    // N tile of the v2 kernels: 128 unless a 64-wide tile wastes less (e.g. N = 320: 5 x 64 exact vs 3 x 128 = 17 % padding)
     // (64-row tiles for the small-M 8x8 level were measured slower than under-filled 128-row tiles: conv_L3 461 vs 586 TF/s)
-    if (w64 < w128) return launch<128, 64, MODE, GEGLU>(p, batch, st);
-    return launch<128, 128, MODE, GEGLU>(p, batch, st);
+    const int bn2 = cdiv(p.N, 64) * 64 < cdiv(p.N, 128) * 128 ? 64 : 128;
+    // v3 (persistent big tiles) unless forced off (V3D_GEMM_IMPL=1/2), forced on (=3), or the tile count fills the CUs badly
+    if (pol.impl != 1 && pol.impl != 2 && batch == 1 && dma_ok && p.N >= 256) {
+        // epilogue-bound GEGLU projections (K = 320): 256 x 128 tile, two blocks per CU
+        if (geglu && (p.K < 640 || pol.v3s >= 2) && pol.v3s && v3_ok(p, 64, 64) && cdiv(p.M, 256) * cdiv(p.N, 128) >= 2ll * cus) {
+            tile(K_V3_256x128_GEGLU, 3, 256, 128, 512);
+            return persistent(2ll * cus);
+        }
+        // measured (profiles/r01f_op_times_v3.txt): v3 wins wherever its tiles fill the CUs about as well as v2's (128 x bn2 tiles, 2 blocks per CU) do
+        const bool want = pol.impl == 3 || fill3 >= 0.9 * fill(128, bn2, 2ll * cus);
+        // (non-GEGLU v3 kernels only carry the hand-managed epilogue: its operand contract on top of the tile-shape one)
+        const bool eok = geglu || (n320 ? e4_ok(p, 96, 80) : e4_ok(p, 128, 64));
+        if (want && eok && (n320 ? v3_ok(p, 96, 80) : v3_ok(p, 128, 128))) {
+            // statistics epilogue: every writer (wave tile x statistics group) stores into its own slot - needs whole groups per wave column (80 / 64 channels)
+            // and gn_rps / (wave tile rows) + 2 slots
+            const bool gn = !geglu && p.gn_stats && (n320 ? 80 : 64) % p.gn_cpg == 0 && p.gn_nslots >= p.gn_rps / (n320 ? 96 : 128) + 2;
+            // GEGLU halves the output width: with waves laid out 4 (M) x 2 (N) a wave owns 128 weight rows = 64 output channels = whole
+            // 128-byte lines of every output row (the 2 x 4 layout wrote 64-byte half lines from two different waves)
+            // measured (tools/gemm_floor.py, M = 147456, N = 2560): K = 320: 396 us vs 416 us (2 x 4) vs 402 us (two 256 x 128 blocks
+            // per CU) vs 421 us (v2); at K >= 640 the 2 x 4 layout with 32-row chunks is ahead again (tools/gemm_sweep.py)
+            tile(n320 ? (gn ? K_V3_192x320_GN : K_V3_192x320) : gn ? K_V3_256_GN : (geglu && p.K < 640) ? K_V3_256_GEGLU42 : K_V3_256, 3, bm3, bn3, 512);
+            pl.gn_in_epilogue = gn;
+            return persistent(cus);
+        }
+    }
+    // v2 / v1: one 128 x bn2 tile per block
+    tile(K_V1, 1, 128, bn2, 256);
+    pl.grid_x = (unsigned)pl.tiles; pl.grid_y = (unsigned)batch;
+    // split-K: the 8x8 level has 180 tiles of 128 x 128 for 256 CUs and contractions of 160-720 steps, so a launch lasts as long as
+    // ONE tile (conv 8x8 1280->1280: 153 us, 444 TF/s).  Splitting the flat (tap, k) range 2-4 ways fills the CUs; the partial sums
+    // meet in an fp32 workspace (one slab per split) and a small finalize kernel applies the epilogue.
+    if (!geglu) {
+        const long long steps = (long long)taps * (p.K / 32);
+        int ways = pol.splitk;
+        if (ways < 0) ways = (pl.tiles * 4 <= (long long)cus * 3 && steps >= 96) ? (int)((3ll * cus + pl.tiles - 1) / pl.tiles) : 1;   // 8x8 conv: 546 / 693 / 617 / 699 TF/s at 1 / 2 / 3 / 4
+        if (ways > 4) ways = 4;
+        if (ways > steps / 32) ways = (int)(steps / 32);
+        if (ways > 1 && batch == 1 && pol.impl != 1 && p.K % 64 == 0 && p.K * 2 <= 65536 && p.N % 4 == 0 && p.ldo % 4 == 0 && vec4_operands(p)) {
+            pl.kernel = K_SPLITK; pl.family = 2; pl.splitk = ways;
+            pl.grid_y = (unsigned)ways;
+            pl.tiles *= ways;
+            return pl;
+        }
+    }
+    const long long stages = (long long)taps * cdiv(p.K, 32);
+    if (pol.impl == 1 || !dma_ok) {
+        // stays v1 (impl 0 / 2 / 3 all land here for v2-class shapes with ragged contractions)
+    } else if (bn2 == 64) {
+        // 64-wide N tiles: a 256 x 64 tile with the 4 waves stacked along M (wave tile 64 x 64) doubles the MFMAs per barrier and halves the weight
+        // re-reads (lin_L0_320x320 433 -> 487, convt_L0_320 568 -> 734 TF/s); BK 64 x 2 stages, BK 32 x 3 when K % 64 != 0
+        tile(p.K % 64 == 0 ? K_V2_256x64_2x64 : K_V2_256x64_3x32, 2, 256, 64, 256);
+    } else if (((geglu && p.K >= 640) || (mode == V3D_GEMM_CONV3X3 && p.K <= 128)) && p.M >= 4096) {
+        // wide GEGLU projections at K >= 640 and the 128-channel VAE convs: 256 x 128 tile on 4 waves (wave tile 128 x 64, 32 MFMAs per barrier,
+        // 25 % fewer LDS-fill bytes per flop), BK 32 x 3 stages: 72 KiB -> 2 blocks / CU (lin_L1_ff1_geglu 662 -> 779, lin_L2_ff1_geglu 708 -> 865 TF/s)
+        tile(K_V2_256x128, 2, 256, 128, 256);
+    } else if (stages <= 40) {
+        // measured on MI355X (profiles/r01_gemm_sweep.txt): short contractions (<= 40 stages of 32: every K <= 1280 linear, the 128-channel
+        // VAE convs) are bound by per-tile fill/drain bubbles -> more co-resident blocks: BK 32 x 3 stages, 48 KiB LDS, 3 blocks / CU
+        pl.kernel = K_V2_128_3x32; pl.family = 2;
+    } else {
+        pl.kernel = p.K % 64 == 0 ? K_V2_128_2x64 : K_V2_128_4x32;      // long contractions prefer fewer barriers per MFMA: BK 64 x 2 stages (one in flight)
+        pl.family = 2;
+    }
+    pl.grid_x = (unsigned)pl.tiles;
+    pl.tiles *= batch;
+    return pl;
 }
 
-}  // namespace
-
-void v3d_note_launch(int family, int bm, int bn, long long tiles, int blocks_per_cu, int streamk) {
-    g_last_launch = V3dLaunchInfo{family, bm, bn, tiles, blocks_per_cu, 0, streamk};
-}
-
-// tests / tools only (not part of the ABI header): out[8] = family, bm, bn, tiles, blocks per CU, split-K ways, stream-K tail, CUs
-extern "C" int v3d_debug_last_gemm_launch(long long* out) {
-    out[0] = g_last_launch.family; out[1] = g_last_launch.bm; out[2] = g_last_launch.bn; out[3] = g_last_launch.tiles;
-    out[4] = g_last_launch.blocks_per_cu; out[5] = g_last_launch.splitk; out[6] = g_last_launch.streamk; out[7] = v3d_num_cus();
-    return 0;
-}
-
-// tests only (not part of the ABI header)
-extern "C" long long v3d_debug_gn_epilogue_launches(void) { return g_gn_epilogue_launches; }
-
-// ---- stream-K plan (device side: gemm_common.h sk_*) ---------------------------------------------------------------------------------------
-namespace {
+// ---- workspaces of the stream-K tail (device side: gemm_common.h sk_*) ---------------------------------------------------------------------------------
 struct SkWorkspace {
     hipStream_t st;
     float* ws;
@@ -1026,96 +953,122 @@ struct SkWorkspace {
     size_t slot_bytes;
     int G;
 };
-std::vector<SkWorkspace> g_sk;       // (one per stream that ever planned a stream-K launch; never freed: captured graphs point into them)
+std::vector<SkWorkspace> g_sk;       // (one per stream that ever launched a stream-K tail; never freed: captured graphs point into them)
 std::mutex g_sk_mu;
 long long g_sk_launches = 0;
-}  // namespace
 
-// would a launch of `ntiles` tiles of `units` granules get a stream-K tail?  Worth it when the partial round leaves >= 1/8 of the chip idle,
-// every block still gets a piece of >= min_units granules, and the idle time it removes ((G - R) / G of a tile, in granules) is >= min_saved:
-// the hand-off costs 10-15 us per owner (publish 245 KB write-through, flag, read back).
-bool v3d_sk_wanted(int ntiles, int units, int min_units, int min_saved) {
-    static int on = -1;
-    if (on < 0) { const char* e = getenv("V3D_STREAMK"); on = e ? atoi(e) : 1; }          // A/B knob: 0 = classic tile assignment everywhere
-    const int G = v3d_num_cus();
-    const int R = ntiles % G;
-    return on && R != 0 && (G - R) * 8 >= G && (long long)R * units / G >= min_units && (long long)(G - R) * units / G >= min_saved;
-}
-
-int v3d_sk_plan(V3dGemmParams& p, int ntiles, int units, int min_units, int min_saved, size_t slot_bytes, void* stream) {
-    p.sk_tail = p.sk_full = 0;
-    p.sk_units = units;
-    p.sk_ws = nullptr;
-    p.sk_flags = nullptr;
-    const int G = v3d_num_cus();
-    const int classic = ntiles < G ? ntiles : G;
-    const int full = ntiles / G, R = ntiles % G;
-    if (!v3d_sk_wanted(ntiles, units, min_units, min_saved)) return classic;
-    hipStream_t st = (hipStream_t)stream;
+// one workspace per stream (launches on one stream run back to back; two streams must not share slots); never allocated inside a capture
+bool sk_workspace(GP& p, size_t slot_bytes, int G, hipStream_t st) {
     std::lock_guard<std::mutex> lock(g_sk_mu);
     const SkWorkspace* w = nullptr;
     for (const SkWorkspace& c : g_sk)
         if (c.st == st && c.slot_bytes >= slot_bytes && c.G == G) w = &c;
     if (!w) {
-        // one workspace per stream (launches on one stream run back to back; two streams must not share slots); never allocated inside a capture
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) { (void)hipGetLastError(); return classic; }
+        if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) { (void)hipGetLastError(); return false; }
         SkWorkspace n = {st, nullptr, nullptr, slot_bytes, G};
         if (hipMalloc(reinterpret_cast<void**>(&n.ws), (size_t)G * slot_bytes) != hipSuccess ||
             hipMalloc(reinterpret_cast<void**>(&n.flags), ((size_t)G * 8 + 16) * 4) != hipSuccess ||
             hipMemset(n.flags, 0, ((size_t)G * 8 + 16) * 4) != hipSuccess) {
             (void)hipGetLastError();
-            return classic;
+            return false;
         }
         g_sk.push_back(n);
         w = &g_sk.back();
     }
-    p.sk_tail = R;
-    p.sk_full = full;
     p.sk_ws = w->ws;
     p.sk_flags = w->flags;
     ++g_sk_launches;
-    return G;
+    return true;
 }
 
-// tests only (CPU): the work list block b of a G-block launch would build for `ntiles` tiles of `units` granules - the device code's own table
-// (gemm_common.h sk_build_table), so the decomposition can be checked for every shape without a GPU.  out[12]: items, donor flag, then two
-// pieces of (tile, u0, u1, role, d0, d1) - the table's layout without its padding.  Returns 0 when no tail is planned for this launch.
-extern "C" int v3d_debug_sk_table(int ntiles, int units, int G, int b, int min_units, int min_saved, int* out) {
-    const int R = ntiles % G;
-    if (R == 0 || (G - R) * 8 < G || (long long)R * units / G < min_units || (long long)(G - R) * units / G < min_saved) return 0;
-    V3dGemmParams p = {};
-    p.sk_tail = R;
-    p.sk_full = ntiles / G;
-    p.sk_units = units;
-    int tab[SK_TAB_BYTES / 4] = {0};
-    sk_build_table(p, b, G, ntiles, units, tab);
-    out[0] = tab[0];
-    out[1] = tab[1];
-    for (int k = 0; k < 2; ++k)
-        for (int j = 0; j < 6; ++j) out[2 + 6 * k + j] = tab[4 + 8 * k + j];
-    return 1;
-}
+// ---- launch: one case per kernel id, no shape logic --------------------------------------------------------------------------------------------------
+constexpr int kNoWorkspace = 1;      // launch_plan: the plan's split-K slab / stream-K workspace cannot be had (stream capture, hipMalloc failure); nothing was launched
 
-// tests only: launches planned with a stream-K tail; hand-offs that gave up waiting (must stay 0)
-extern "C" long long v3d_debug_sk_launches(void) { return g_sk_launches; }
-extern "C" long long v3d_debug_sk_timeouts(void) {
-    long long t = 0;
-    std::lock_guard<std::mutex> lock(g_sk_mu);
-    for (const SkWorkspace& c : g_sk) {
-        unsigned v = 0;
-        if (hipMemcpy(&v, c.flags + (size_t)c.G * 8, 4, hipMemcpyDeviceToHost) == hipSuccess) t += v;
+template <int MODE, bool GEGLU>
+int launch_kernel(const GemmPlan& pl, GP& p, hipStream_t st, int& occ) {
+    const int ntiles = (int)pl.tiles;
+    switch (pl.kernel) {
+        case K_V1:
+            if (pl.bn == 64) V3D_LAUNCH((gemm_kernel_v1<128, 64, MODE, GEGLU>), p);
+            else V3D_LAUNCH((gemm_kernel_v1<128, 128, MODE, GEGLU>), p);
+            break;
+        case K_V2_128_2x64: V3D_LAUNCH((gemm_kernel_v2<128, 128, 2, 2, 2, 2, MODE, GEGLU>), p); break;
+        case K_V2_128_3x32: V3D_LAUNCH((gemm_kernel_v2<128, 128, 2, 2, 3, 1, MODE, GEGLU>), p); break;
+        case K_V2_128_4x32: V3D_LAUNCH((gemm_kernel_v2<128, 128, 2, 2, 4, 1, MODE, GEGLU>), p); break;
+        case K_V2_256x64_2x64: V3D_LAUNCH((gemm_kernel_v2<256, 64, 4, 1, 2, 2, MODE, GEGLU>), p); break;
+        case K_V2_256x64_3x32: V3D_LAUNCH((gemm_kernel_v2<256, 64, 4, 1, 3, 1, MODE, GEGLU>), p); break;
+        case K_V2_256x128: V3D_LAUNCH((gemm_kernel_v2<256, 128, 2, 2, 3, 1, MODE, GEGLU>), p); break;
+        case K_SPLITK:
+            if constexpr (!GEGLU) {
+                float* ws = splitk_workspace((size_t)pl.splitk * (size_t)p.M * (size_t)p.N, st);
+                if (!ws) return kNoWorkspace;
+                GP q = p;                 // the split launch: plain fp32 partial sums, slab `split`
+                q.split_n = pl.splitk;
+                q.out = ws; q.out_fp32 = 1; q.ldo = p.N; q.sO = p.M * p.N; q.sA = 0; q.sW = 0;
+                q.bias = nullptr; q.add = nullptr; q.res1 = nullptr; q.res2 = nullptr; q.coef = nullptr;
+                q.c_acc = 1.f; q.c_res1 = 0.f; q.c_res2 = 0.f;
+                if (pl.bn == 64) V3D_LAUNCH((gemm_kernel_v2<128, 64, 2, 2, 2, 2, MODE, GEGLU>), q);
+                else V3D_LAUNCH((gemm_kernel_v2<128, 128, 2, 2, 2, 2, MODE, GEGLU>), q);
+                p.split_n = pl.splitk;
+                p.ws = ws;
+                hipLaunchKernelGGL(splitk_finalize_kernel, dim3((unsigned)((p.M * (p.N / 4) + 255) / 256)), dim3(256), 0, st, p);
+                return v3d_check_launch("v3d_gemm(split-K)");
+            }
+            break;
+        // epilogue chunk of the generic v3 kernel: 2 row fragments for GEGLU (its staged rows are half as wide), 1 otherwise (LDS budget next to the ring)
+        case K_V3_256: V3D_LAUNCH((gemm_kernel_v3<256, 256, 2, 4, MODE, GEGLU, GEGLU ? 2 : 1>), p, ntiles); break;
+        case K_V3_256_GEGLU42:
+            if constexpr (GEGLU) V3D_LAUNCH((gemm_kernel_v3<256, 256, 4, 2, MODE, GEGLU, 1>), p, ntiles);
+            break;
+        case K_V3_256x128_GEGLU:
+            if constexpr (GEGLU && MODE == V3D_GEMM_LINEAR) V3D_LAUNCH((gemm_kernel_v3<256, 128, 4, 2, MODE, GEGLU, 1, 3, 0>), p, ntiles);
+            break;
+        case K_V3_256_GN:
+            if constexpr (!GEGLU) V3D_LAUNCH((gemm_kernel_v3<256, 256, 2, 4, MODE, GEGLU, 1, 4, 16, true>), p, ntiles);
+            break;
+        case K_V3_192x320:
+            if constexpr (!GEGLU) V3D_LAUNCH((gemm_kernel_v3<192, 320, 2, 4, MODE, GEGLU, 1>), p, ntiles);
+            break;
+        case K_V3_192x320_GN:
+            if constexpr (!GEGLU) V3D_LAUNCH((gemm_kernel_v3<192, 320, 2, 4, MODE, GEGLU, 1, 4, 16, true>), p, ntiles);
+            break;
+        case K_V6:
+            if constexpr ((MODE == V3D_GEMM_LINEAR || MODE == V3D_GEMM_CONVT3) && !GEGLU) {
+                V3D_LAUNCH((gemm_kernel_v6<192, 160, 3, MODE>), p, ntiles);
+                return v3d_check_launch("v3d_gemm(v6)");
+            }
+            break;
     }
-    return t;
+    return v3d_check_launch("v3d_gemm");
 }
 
-namespace {
-int run_mode(const v3d_gemm_args* a, GP& p, hipStream_t st);
+int launch_plan(const GemmPlan& pl, GP& p0, hipStream_t st) {
+    GP p = p0;
+    p.mt = pl.mt; p.nt = pl.nt; p.group_m = pl.group_m;
+    int occ = 1, rc;
+    if (pl.family == 5) {
+        p.sk_units = pl.sk_units;
+        if (pl.sk_tail) {
+            if (!sk_workspace(p, pl.sk_slot_bytes, (int)pl.grid_x, st)) return kNoWorkspace;
+            p.sk_tail = pl.sk_tail; p.sk_full = pl.sk_full;
+        }
+        rc = v3d_conv_halo_launch(p, pl.kernel - K_HALO1 + 1, (int)pl.grid_x, (int)pl.tiles, (void*)st);
+    } else if (pl.mode == V3D_GEMM_LINEAR) {
+        rc = pl.geglu ? launch_kernel<V3D_GEMM_LINEAR, true>(pl, p, st, occ) : launch_kernel<V3D_GEMM_LINEAR, false>(pl, p, st, occ);
+    } else if (pl.mode == V3D_GEMM_CONV3X3) {
+        rc = launch_kernel<V3D_GEMM_CONV3X3, false>(pl, p, st, occ);
+    } else {
+        rc = launch_kernel<V3D_GEMM_CONVT3, false>(pl, p, st, occ);
+    }
+    if (rc == kNoWorkspace) return rc;
+    if (pl.family == 3 && pl.gn_in_epilogue) ++g_gn_epilogue_launches;
+    g_last_launch = V3dLaunchInfo{pl.family, pl.bm, pl.bn, pl.tiles, occ, pl.splitk, pl.sk_tail};
+    return rc;
 }
 
-namespace {
-// argument checks + the kernels' parameter block; *halo = the LDS-haloed kernel variant that takes the launch (conv.hip), 0 = none
-int fill_params(const v3d_gemm_args* a, GP& p, int* halo) {
+// argument checks (all of them) + the kernels' parameter block
+int fill_params(const v3d_gemm_args* a, GP& p) {
     V3D_REQUIRE(a != nullptr, "v3d_gemm: null args");
     V3D_REQUIRE(a->A && a->W && a->out, "v3d_gemm: null A/W/out");
     V3D_REQUIRE(a->M > 0 && a->N > 0 && a->K > 0, "v3d_gemm: bad M/N/K (%lld,%lld,%lld)", (long long)a->M, (long long)a->N, (long long)a->K);
@@ -1151,7 +1104,7 @@ int fill_params(const v3d_gemm_args* a, GP& p, int* halo) {
     p.halo_rows = a->mode == V3D_GEMM_CONVT3 ? a->halo_rows : 0;
     p.sA = a->sA; p.sW = a->sW; p.sO = a->sO;
     p.mt = p.nt = 0;
-    p.group_m = -1;        // tile walk: the heuristic of tile_coords (v6 sets its own)
+    p.group_m = -1;
     p.split_n = 1;
     p.ws = nullptr;
     p.sk_tail = p.sk_full = p.sk_units = 0; p.sk_ws = nullptr; p.sk_flags = nullptr;
@@ -1179,49 +1132,8 @@ int fill_params(const v3d_gemm_args* a, GP& p, int* halo) {
         V3D_REQUIRE(tb <= kMaxBufBytes && a->batch == 1 && !a->geglu, "v3d_gemm: gn_in_table too large / batched / GEGLU");
         p.gn_in_bytes = (unsigned)tb;
     }
-    *halo = 0;
-    if (a->mode == V3D_GEMM_CONV3X3) {
-        p.upshift = a->up - 1;
-        p.pad_lo = a->pad_mode ? 0 : 1;
-    }
-    if (a->gn_in_table && a->batch == 1 && !a->geglu && (a->mode == V3D_GEMM_CONV3X3 || a->mode == V3D_GEMM_CONVT3))
-        *halo = v3d_conv_halo_variant(p, a->mode);
-    return V3D_OK;
-}
-}  // namespace
-
-extern "C" int v3d_gemm_gn_in_supported(const v3d_gemm_args* a) {
-    GP p;
-    int halo = 0;
-    if (!a || !a->gn_in_table || fill_params(a, p, &halo) != V3D_OK) return 0;
-    return halo != 0;
-}
-
-extern "C" int v3d_gemm(const v3d_gemm_args* a, v3d_stream_t stream) {
-    GP p;
-    int halo = 0;
-    const int frc = fill_params(a, p, &halo);
-    if (frc != V3D_OK) return frc;
-    hipStream_t st = (hipStream_t)stream;
-    if (halo) return v3d_conv_halo_launch(p, halo, stream);      // (its epilogue gathers gn_stats itself)
-    V3D_REQUIRE(!a->gn_in_table, "v3d_gemm: gn_in_table is set but this shape is not one of the LDS-haloed kernels' (v3d_gemm_gn_in_supported): "
-                                 "normalise the input with v3d_groupnorm_apply first");
-    if (p.gn_stats) {
-        g_gn_in_epilogue = false;
-        const int rc = run_mode(a, p, st);
-        if (rc != V3D_OK || g_gn_in_epilogue) return rc;
-        // the kernel that ran has no statistics epilogue (v1 / v2 tiles, split-K, ragged shapes): same result from the stand-alone kernel
-        return v3d_groupnorm_stats(a->out, a->N, nullptr, 0, a->gn_stats, a->gn_nslots, a->M / a->gn_rps, a->gn_rps, 32, 1, stream);
-    }
-    return run_mode(a, p, st);
-}
-
-namespace {
-int run_mode(const v3d_gemm_args* a, GP& p, hipStream_t st) {
     switch (a->mode) {
-        case V3D_GEMM_LINEAR:
-            if (a->geglu) return dispatch<V3D_GEMM_LINEAR, true>(p, a->batch, st);
-            return dispatch<V3D_GEMM_LINEAR, false>(p, a->batch, st);
+        case V3D_GEMM_LINEAR: break;
         case V3D_GEMM_CONV3X3:
             V3D_REQUIRE(a->up == 1 || a->up == 2, "v3d_gemm: up must be 1 or 2");
             V3D_REQUIRE(a->stride == 1 || a->stride == 2, "v3d_gemm: stride must be 1 or 2");
@@ -1230,7 +1142,7 @@ int run_mode(const v3d_gemm_args* a, GP& p, hipStream_t st) {
             V3D_REQUIRE(a->pad_mode == 0 || a->pad_mode == 1, "v3d_gemm: pad_mode must be 0 or 1");
             p.upshift = a->up - 1;
             p.pad_lo = a->pad_mode ? 0 : 1;
-            return dispatch<V3D_GEMM_CONV3X3, false>(p, a->batch, st);
+            break;
         case V3D_GEMM_CONVT3:
             V3D_REQUIRE(a->T > 0 && a->S > 0, "v3d_gemm: convt3 needs T,S");
             V3D_REQUIRE(a->halo_rows >= 0, "v3d_gemm: halo_rows must be >= 0");
@@ -1239,10 +1151,94 @@ int run_mode(const v3d_gemm_args* a, GP& p, hipStream_t st) {
                 V3D_REQUIRE(a->a_row0 >= a->halo_rows && a->a_rows >= a->a_row0 + a->M + a->halo_rows, "v3d_gemm: split-halo layout: A must hold halo_rows rows on either side of the M local rows");
                 V3D_REQUIRE(a->tmin >= -1 && a->tmax <= a->T, "v3d_gemm: split-halo layout carries one halo frame per side");
             }
-            return dispatch<V3D_GEMM_CONVT3, false>(p, a->batch, st);
+            break;
         default:
             v3d_set_error("v3d_gemm: unknown mode %d", a->mode);
             return V3D_ERR_ARG;
     }
+    return V3D_OK;
 }
+
 }  // namespace
+
+// tests / tools only (not part of the ABI header): out[8] = family, bm, bn, tiles, blocks per CU, split-K ways, stream-K tail, CUs
+extern "C" int v3d_debug_last_gemm_launch(long long* out) {
+    out[0] = g_last_launch.family; out[1] = g_last_launch.bm; out[2] = g_last_launch.bn; out[3] = g_last_launch.tiles;
+    out[4] = g_last_launch.blocks_per_cu; out[5] = g_last_launch.splitk; out[6] = g_last_launch.streamk; out[7] = v3d_num_cus();
+    return 0;
+}
+
+// tests only (CPU): what plan_gemm chooses for these arguments on a device of `cus` CUs under policy5 = {IMPL, SPLITK, V3S, V6, STREAMK} (NULL: the
+// environment's).  Pointers in `a` are only inspected for null-ness and alignment.  out[10] = kernel id, family, bm, bn, tiles, grid, split-K ways,
+// stream-K tail tiles (0 = classic), gn_in_epilogue, number of kernel ids
+extern "C" int v3d_debug_gemm_plan(const v3d_gemm_args* a, int cus, const int* policy5, long long* out) {
+    GP p;
+    const int frc = fill_params(a, p);
+    if (frc != V3D_OK) return frc;
+    const GemmPolicy pol = policy5 ? GemmPolicy{policy5[0], policy5[1], policy5[2], policy5[3], policy5[4]} : env_policy();
+    const GemmPlan pl = plan_gemm(p, a->mode, a->geglu != 0, a->batch, cus, pol);
+    out[0] = pl.kernel; out[1] = pl.family; out[2] = pl.bm; out[3] = pl.bn; out[4] = pl.tiles; out[5] = (long long)pl.grid_x * pl.grid_y;
+    out[6] = pl.splitk; out[7] = pl.sk_tail; out[8] = pl.gn_in_epilogue; out[9] = K_COUNT;
+    return V3D_OK;
+}
+
+// tests only (not part of the ABI header)
+extern "C" long long v3d_debug_gn_epilogue_launches(void) { return g_gn_epilogue_launches; }
+
+// tests only (CPU): the work list block b of a G-block launch would build for `ntiles` tiles of `units` granules - the device code's own table
+// (gemm_common.h sk_build_table), so the decomposition can be checked for every shape without a GPU.  out[12]: items, donor flag, then two
+// pieces of (tile, u0, u1, role, d0, d1) - the table's layout without its padding.  Returns 0 when no tail is planned for this launch.
+extern "C" int v3d_debug_sk_table(int ntiles, int units, int G, int b, int min_units, int min_saved, int* out) {
+    const int R = ntiles % G;
+    if (R == 0 || (G - R) * 8 < G || (long long)R * units / G < min_units || (long long)(G - R) * units / G < min_saved) return 0;
+    V3dGemmParams p = {};
+    p.sk_tail = R;
+    p.sk_full = ntiles / G;
+    p.sk_units = units;
+    int tab[SK_TAB_BYTES / 4] = {0};
+    sk_build_table(p, b, G, ntiles, units, tab);
+    out[0] = tab[0];
+    out[1] = tab[1];
+    for (int k = 0; k < 2; ++k)
+        for (int j = 0; j < 6; ++j) out[2 + 6 * k + j] = tab[4 + 8 * k + j];
+    return 1;
+}
+
+// tests only: launches with a stream-K tail; hand-offs that gave up waiting (must stay 0)
+extern "C" long long v3d_debug_sk_launches(void) { return g_sk_launches; }
+extern "C" long long v3d_debug_sk_timeouts(void) {
+    long long t = 0;
+    std::lock_guard<std::mutex> lock(g_sk_mu);
+    for (const SkWorkspace& c : g_sk) {
+        unsigned v = 0;
+        if (hipMemcpy(&v, c.flags + (size_t)c.G * 8, 4, hipMemcpyDeviceToHost) == hipSuccess) t += v;
+    }
+    return t;
+}
+
+extern "C" int v3d_gemm_gn_in_supported(const v3d_gemm_args* a) {
+    GP p;
+    if (!a || !a->gn_in_table || fill_params(a, p) != V3D_OK) return 0;
+    return plan_gemm(p, a->mode, false, 1, v3d_num_cus(), env_policy()).kernel != K_NONE;
+}
+
+extern "C" int v3d_gemm(const v3d_gemm_args* a, v3d_stream_t stream) {
+    GP p;
+    const int frc = fill_params(a, p);
+    if (frc != V3D_OK) return frc;
+    hipStream_t st = (hipStream_t)stream;
+    GemmPolicy pol = env_policy();
+    GemmPlan pl = plan_gemm(p, a->mode, a->geglu != 0, a->batch, v3d_num_cus(), pol);
+    V3D_REQUIRE(pl.kernel != K_NONE, "v3d_gemm: gn_in_table is set but this shape is not one of the LDS-haloed kernels' (v3d_gemm_gn_in_supported): "
+                                     "normalise the input with v3d_groupnorm_apply first");
+    int rc = launch_plan(pl, p, st);
+    if (rc == kNoWorkspace) {      // the same call without the feature that needs a workspace
+        pol.splitk = 0;
+        pol.streamk = 0;
+        pl = plan_gemm(p, a->mode, a->geglu != 0, a->batch, v3d_num_cus(), pol);
+        rc = launch_plan(pl, p, st);
+    }
+    if (rc != V3D_OK || !p.gn_stats || pl.gn_in_epilogue) return rc;
+    // the kernel that ran has no statistics epilogue (v1 / v2 tiles, split-K, ragged shapes): same result from the stand-alone kernel
+    return v3d_groupnorm_stats(a->out, a->N, nullptr, 0, a->gn_stats, a->gn_nslots, a->M / a->gn_rps, a->gn_rps, 32, 1, stream);
+}

@@ -64,14 +64,12 @@ struct V3dLaunchInfo {
     long long tiles;
     int blocks_per_cu, splitk, streamk;
 };
-void v3d_note_launch(int family, int bm, int bn, long long tiles, int blocks_per_cu, int streamk);
-// conv.hip: the LDS-haloed kernels (GroupNorm + SiLU in the operand path)
+// conv.hip: the LDS-haloed kernels (GroupNorm + SiLU in the operand path).  gemm.hip's plan_gemm asks which variant takes a call (pure) and its
+// launch_plan hands over the planned launch: p.mt / nt / sk_* filled, `grid` blocks for `ntiles` tiles
 int v3d_conv_halo_variant(const V3dGemmParams& p, int mode);          // 0 = not one of their shapes
-int v3d_conv_halo_launch(const V3dGemmParams& p, int variant, void* stream);
-// gemm.hip: stream-K plan of a persistent launch (fills p.sk_*, returns the grid): ntiles tiles of `units` split granules on the device's CUs;
-// slot_bytes = one block's accumulators in fp32.  Leaves the classic assignment (sk_tail = 0) when the tail round is full enough or too thin.
-int v3d_sk_plan(V3dGemmParams& p, int ntiles, int units, int min_units, int min_saved, size_t slot_bytes, void* stream);
-bool v3d_sk_wanted(int ntiles, int units, int min_units, int min_saved);
+int v3d_conv_halo_launch(const V3dGemmParams& p, int variant, int grid, int ntiles, void* stream);
+// host: the LDS-DMA main loops step through K in whole 32-k slices, and a padding lane's zero-page pointer advances by up to K * 2 bytes
+inline bool v3d_k_steps_ok(const V3dGemmParams& p) { return p.K % 32 == 0 && p.K * 2 <= 65536; }
 
 namespace {
 
@@ -874,7 +872,7 @@ __device__ __forceinline__ void e4_retire_tile(const GP& p, f32x4 (&acc)[MF][NF]
 // ---- stream-K tail ------------------------------------------------------------------------------------------------------------------------
 // A persistent launch of `ntiles` tiles on G blocks (one per CU) leaves CUs idle in its last round unless ntiles % G == 0: the 32 x 32 level
 // of the U-Net runs 384 tiles (1.5 rounds: half the chip idles through the second), the 16 x 16 level 192 (a quarter idles throughout).  With a
-// plan (v3d_sk_plan) the R = ntiles % G tiles of that last round are cut along K into R * U granules (U per tile) and block b takes the
+// plan (gemm.hip plan_gemm) the R = ntiles % G tiles of that last round are cut along K into R * U granules (U per tile) and block b takes the
 // granules [b R U / G, (b + 1) R U / G): at most two pieces of two neighbouring tiles.  A piece that starts inside a tile is a DONOR piece:
 // the block runs it FIRST, parks its fp32 accumulators in its workspace slot (16-byte write-through stores, MI355X_MICROARCH.md "publish-large")
 // and raises one flag per wave.  A piece that starts a tile is the OWNER piece: the block runs it LAST, then adds the donors' partials in

@@ -169,7 +169,8 @@ class HipOps(OpsBase):
 
     def last_gemm_launch(self) -> dict:
         """What the last `gemm` of this thread actually launched (the library's own record, gemm.hip v3d_debug_last_gemm_launch): kernel family
-        (1 = v1, 2 = v2, 3 = persistent v3, 5 = LDS-haloed, 6 = two persistent 4-wave blocks per CU), tile, tile count, co-resident blocks per CU, split-K ways, stream-K tail - and `fill`,
+        (1 = v1, 2 = v2 incl. split-K, 3 = persistent v3, 5 = LDS-haloed, 6 = v6: two persistent 4-wave blocks per CU; the table at gemm.hip plan_gemm lists
+        every kernel), tile, tile count, co-resident blocks per CU, split-K ways, stream-K tail - and `fill`,
         the fraction of the CU slots the launch keeps busy over its rounds (1.0 with a stream-K tail: the last round is shared out)."""
         fn = self.lib.v3d_debug_last_gemm_launch
         fn.restype, fn.argtypes = c_i32, [c_vp]
@@ -180,6 +181,17 @@ class HipOps(OpsBase):
         tiles_eff = tiles * max(1, sk)
         fill = 1.0 if tail else tiles_eff / (-(-tiles_eff // slots) * slots) if tiles_eff else 0.0
         return {"family": fam, "bm": bm, "bn": bn, "tiles": tiles, "blocks_per_cu": bpc, "splitk": sk, "streamk_tail": tail, "cus": cus, "fill": fill}
+
+    def gemm_plan(self, g: GemmCall) -> dict:
+        """What `gemm(g)` would launch on this device: the library's planner alone (gemm.hip plan_gemm through v3d_debug_gemm_plan), nothing runs.
+        `kernel` is the planner's kernel id; family / bm / bn / tiles / splitk / streamk_tail mean what they mean in `last_gemm_launch`."""
+        fn = self.lib.v3d_debug_gemm_plan
+        fn.restype, fn.argtypes = c_i32, [C.POINTER(_GemmArgs), c_i32, c_vp, c_vp]
+        o = (C.c_longlong * 10)()
+        a = self._gemm_args(g)
+        self._check(fn(C.byref(a), self.cu_count, None, C.cast(o, c_vp)), "v3d_debug_gemm_plan")
+        kid, fam, bm, bn, tiles, grid, sk, tail, gn, _ = (int(v) for v in o)
+        return {"kernel": kid, "family": fam, "bm": bm, "bn": bn, "tiles": tiles, "grid": grid, "splitk": sk, "streamk_tail": tail, "gn_in_epilogue": bool(gn)}
 
     def check_health(self):
         n = self.streamk_timeouts()

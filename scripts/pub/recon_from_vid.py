@@ -8,7 +8,8 @@
 --video takes the .npy that V3D_512.py --save writes without mediapy, a folder of PNG frames (sorted by name), or an .mp4 when mediapy is
 installed.  --input_path generates the orbit in-process (scripts/pub/V3D_512.py sample_one) and hands model.last_frames_u8 over on the device.
 Writes <model_path>/point_cloud/iteration_<n>/point_cloud.ply (the reference's layout and attributes).  SH degree 0 only; LPIPS is not
-available (pass --lambda_lpips 0)."""
+available (pass --lambda_lpips 0).  --save_mesh fuses depth maps of the training views into a TSDF and writes a coloured triangle mesh
+(v3d_amd/recon/geometry.py); --render_depth N writes N turntable frames of normalised depth."""
 from __future__ import annotations
 
 import argparse
@@ -56,7 +57,7 @@ def save_frames(frames: np.ndarray, folder: str):
         Image.fromarray(f).save(os.path.join(folder, f"{i:03d}.png"))
 
 
-def main(argv=None):
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("-w", "--white_background", action="store_true")
     ap.add_argument("--sh_degree", type=int, default=0)
@@ -77,7 +78,18 @@ def main(argv=None):
     ap.add_argument("--checkpoint_path", default=None)
     ap.add_argument("--num_steps", type=int, default=None)
     ap.add_argument("--render_orbit", type=int, default=0, help="write N turntable frames of the result to <model_path>/orbit/")
+    ap.add_argument("--save_mesh", nargs="?", const="", default=None, metavar="PATH",
+                    help="fuse the orbit views' depth into a TSDF and write a coloured triangle mesh (default PATH: <model_path>/mesh.ply)")
+    ap.add_argument("--mesh_resolution", type=int, default=256, help="voxels per axis of the TSDF volume of --save_mesh (at most 512)")
+    ap.add_argument("--render_depth", type=int, default=0, help="write N turntable frames of normalised depth to <model_path>/depth.npy (float32)")
+    return ap
+
+
+def main(argv=None):
+    ap = build_parser()
     a = ap.parse_args(argv)
+    if a.save_mesh is not None and not 2 <= a.mesh_resolution <= 512:
+        ap.error("--mesh_resolution must lie in 2 .. 512")
     from v3d_amd.recon import train
     try:
         train.check_options(a.sh_degree, a.lambda_lpips)
@@ -112,6 +124,21 @@ def main(argv=None):
         orbit = train.render_orbit(g, a.render_orbit, a.radius, a.elevation, a.fov, reso, a.white_background)
         save_frames(orbit, os.path.join(a.model_path, "orbit"))
         print(f"[recon] {a.render_orbit} turntable frames -> {os.path.join(a.model_path, 'orbit')}")
+    if a.render_depth:
+        from v3d_amd.recon import geometry
+        path = os.path.join(a.model_path, "depth.npy")
+        os.makedirs(a.model_path, exist_ok=True)
+        np.save(path, geometry.render_depth_orbit(g, a.render_depth, a.radius, a.elevation, a.fov, int(frames.shape[1]), a.white_background))
+        print(f"[recon] {a.render_depth} normalised depth frames -> {path}")
+    if a.save_mesh is not None:
+        from v3d_amd.recon import geometry
+        from v3d_amd.recon.cameras import orbit_cameras
+        path = a.save_mesh or os.path.join(a.model_path, "mesh.ply")
+        cams, _ = orbit_cameras(int(frames.shape[0]), a.radius, a.elevation, a.fov, int(frames.shape[1]))
+        vol = geometry.fuse_tsdf(g, cams, resolution=a.mesh_resolution, bg=[1.0, 1.0, 1.0] if a.white_background else [0.0, 0.0, 0.0])
+        verts, faces, colors = geometry.extract_mesh(vol)
+        geometry.save_mesh_ply(path, verts, faces, colors)
+        print(f"[recon] mesh: {verts.shape[0]} vertices, {faces.shape[0]} triangles at {a.mesh_resolution}^3 -> {path}")
 
 
 if __name__ == "__main__":

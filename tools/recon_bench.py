@@ -2,7 +2,9 @@
 --lambda_lpips 0 --num_pts 100000 -w, 4000 iterations.  The orbit is a seeded 3000-Gaussian scene rendered by the HIP forward (no
 checkpoints needed).  Prints one JSON line: total seconds, ms per iteration, Gaussian count after densification, final training-view PSNR.
 
-    python tools/recon_bench.py [--iterations 4000] [--reso 512]
+    python tools/recon_bench.py [--iterations 4000] [--reso 512] [--mesh 256]
+--mesh N adds the time of the mesh stage on the result (v3d_amd/recon/geometry.py: depth / alpha maps and TSDF fusion of the training views at
+N^3, surface nets, the PLY), second of two runs.
     rocprofv3 --kernel-trace --stats -d /tmp/rp -o rp -- python tools/recon_bench.py --iterations 300     # per-kernel split
 """
 from __future__ import annotations
@@ -27,6 +29,7 @@ def main():
     ap.add_argument("--reso", type=int, default=512)
     ap.add_argument("--views", type=int, default=18)
     ap.add_argument("--num_pts", type=int, default=100_000)
+    ap.add_argument("--mesh", type=int, default=0, metavar="N", help="also time fuse_tsdf + extract_mesh + save_mesh_ply at N^3")
     a = ap.parse_args()
     import gs_dense_ref as D
     from v3d_amd.recon import rasterize as RZ
@@ -43,7 +46,27 @@ def main():
     bg = torch.ones(3, device="cuda")
     with torch.no_grad():
         ps = [TR.psnr(RZ.render(c, g, bg)["render"].clamp(0, 1), gt[i]) for i, c in enumerate(cams)]
-    print(json.dumps({"iterations": a.iterations, "reso": a.reso, "views": a.views, "num_pts": a.num_pts, "seconds": round(st["seconds"], 2),
+    mesh = {}
+    if a.mesh:
+        import tempfile
+        import time
+
+        from v3d_amd.recon import geometry as GE
+        for _ in range(2):      # (the first run loads the library and sizes the allocator)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            vol = GE.fuse_tsdf(g, cams, resolution=a.mesh)
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            verts, faces, colors = GE.extract_mesh(vol)
+            torch.cuda.synchronize()
+            t2 = time.perf_counter()
+            with tempfile.TemporaryDirectory() as d:
+                GE.save_mesh_ply(os.path.join(d, "mesh.ply"), verts, faces, colors)
+            t3 = time.perf_counter()
+        mesh = {"mesh_resolution": a.mesh, "mesh_fuse_ms": round(1000 * (t1 - t0), 2), "mesh_extract_ms": round(1000 * (t2 - t1), 2),
+                "mesh_ply_ms": round(1000 * (t3 - t2), 2), "mesh_vertices": int(verts.shape[0]), "mesh_triangles": int(faces.shape[0])}
+    print(json.dumps({**mesh, "iterations": a.iterations, "reso": a.reso, "views": a.views, "num_pts": a.num_pts, "seconds": round(st["seconds"], 2),
                       "ms_per_iter": round(1000 * st["seconds"] / a.iterations, 3), "num_gaussians": st["num_gaussians"],
                       "psnr_mean": round(float(np.mean(ps)), 2), "device": torch.cuda.get_device_name(0)}))
 

@@ -86,6 +86,8 @@ def build(force: bool = False, verbose: bool = True) -> str:
         build_comm(force=force, verbose=verbose)
     except Exception as e:      # noqa: BLE001
         print(f"[v3d_amd.build] WARNING: libv3d_comm.so not built ({str(e).splitlines()[0]}); the kernel library is unaffected", file=sys.stderr)
+    # libv3d_recon.so is NOT optional: v3d_amd/recon/geometry.py has no other path to its kernels, so a failure raises
+    build_recon(force=force, verbose=verbose)
     return LIB
 
 
@@ -108,6 +110,30 @@ def build_comm(force: bool = False, verbose: bool = True) -> str:
         if r.returncode != 0:
             raise RuntimeError(f"hipcc failed for {COMM_SRC}:\n{r.stdout}\n{r.stderr}")
     return COMM_LIB
+
+
+RECON_CSRC = os.path.join(HERE, "csrc_recon")
+RECON_LIB = os.path.join(LIBDIR, "libv3d_recon.so")
+
+
+def build_recon(force: bool = False, verbose: bool = True) -> str:
+    """libv3d_recon.so (include/v3d_recon.h): depth / alpha maps, TSDF fusion and surface extraction of the reconstruction step, from
+    csrc_recon/*.hip - its own library, so the kernel library's sources (and the profile that records their hash) stay as they are.  The
+    flags of gs.hip, -fno-fast-math included: the maps are held to an fp64 restatement (tests/recon_geom_ref.py)."""
+    os.makedirs(LIBDIR, exist_ok=True)
+    inc = os.path.join(os.path.dirname(HERE), "include")
+    srcs = sorted(os.path.join(RECON_CSRC, f) for f in os.listdir(RECON_CSRC) if f.endswith(".hip"))
+    hdrs = [os.path.join(inc, "v3d_recon.h"), os.path.join(inc, "v3d_hip.h")]
+    if force or _stale(RECON_LIB, srcs + hdrs):
+        cmd = [_hipcc(), *FLAGS, "-fno-fast-math", "-I", inc, "-shared", *srcs, "-o", RECON_LIB]
+        if verbose:
+            print("[v3d_amd.build]", " ".join(cmd), flush=True)
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        if r.returncode != 0:
+            raise RuntimeError(f"hipcc failed for {RECON_CSRC}:\n{r.stdout}\n{r.stderr}")
+        if verbose and r.stderr.strip():
+            print(r.stderr, file=sys.stderr)
+    return RECON_LIB
 
 
 if __name__ == "__main__":

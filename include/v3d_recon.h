@@ -1,4 +1,4 @@
-/* v3d_recon.h - C ABI of libv3d_recon.so (v3d_amd/csrc_recon/geom.hip): geometry from the reconstructed splats.  Forward only; its own
+/* v3d_recon.h - C ABI of libv3d_recon.so (v3d_amd/csrc_recon/): geometry from the reconstructed splats.  Forward only; its own
  * library, beside libv3d_hip.so whose rasterizer intermediates it consumes (include/v3d_hip.h "Gaussian-splat reconstruction").
  *   per view:  v3d_recon_depth_alpha (expected depth + accumulated alpha of every pixel)  ->  v3d_recon_tsdf_integrate (one view into the volume)
  *   once:      v3d_recon_cells_flag -> scan -> v3d_recon_cells_vertices;  v3d_recon_edges_flag -> scan -> v3d_recon_edges_faces
@@ -54,6 +54,62 @@ int v3d_recon_edges_flag(const float* tsdf_sum, const float* weight, int32_t N, 
  * (cell_offsets), wound so that the normal points from the negative to the positive voxel.  faces [2 n_edges][3]. */
 int v3d_recon_edges_faces(const float* tsdf_sum, const float* weight, int32_t N, const int32_t* cell_offsets, const int32_t* edge_flags,
                           const int32_t* edge_offsets, int32_t* faces, v3d_stream_t stream);
+
+/* ---- Mesh rasterizer (v3d_amd/csrc_recon/meshrast.hip; host side: v3d_amd/recon/mesh_render.py) ------------------------------------------
+ * Renders the extracted triangle mesh from one camera.  Forward only, no atomics, bit-reproducible.  Per view:
+ *   v3d_recon_mesh_project -> v3d_recon_mesh_face_setup -> scan of tiles_touched -> v3d_recon_mesh_duplicate_keys -> sort of the pairs on
+ *   32 + bits(tiles) key bits -> v3d_recon_mesh_tile_ranges -> v3d_recon_mesh_render
+ * (the binning of the splat rasterizer; the scan and the sort are v3d_gs_scan and v3d_gs_radix_sort_pairs of libv3d_hip.so, called by the
+ * host, which reads the scan's total back and refuses one above INT32_MAX).
+ * Pixel (i, j) has its centre at coordinate (i, j) (the convention of the splat rasterizer's ndc2Pix).  Vertices are snapped to a grid of
+ * 2^subpixel_bits steps per pixel (0 .. 8 bits); coverage is decided on those integers alone, with int64 edge functions.  Images are at most
+ * 4096 pixels on a side.
+ * Marked vertices: view z <= 0.2, a position that is not finite, or one beyond 2^28 sub-pixel steps from the origin (the edge functions must
+ * stay inside int64).  A face that uses a marked vertex is not drawn: THERE IS NO NEAR-PLANE CLIPPING, a face with a corner at z <= 0.2 is
+ * dropped whole.  The orbit cameras sit at radius 2 around a volume of half-extent about 1.1, so on the documented path no vertex comes
+ * nearer than 0.4 and this never happens.
+ * Front faces: view axes are x right, y down, z forward, and pixels run the same way, so a face whose corners run counter-clockwise seen from
+ * outside (outward normal, the winding v3d_recon_edges_faces writes) and which looks at the camera has a NEGATIVE doubled area
+ * (b - a) x (c - a) of its snapped corners.  cull = 1 drops the faces of positive area. */
+#define V3D_RECON_MESH_MAX_IMAGE 4096
+#define V3D_RECON_MESH_MAX_SUBPIXEL_BITS 8
+
+/* One thread per vertex, verts [V][3].  View z through cam->view and the pixel position through cam->proj, the statements of the TSDF pass:
+ * px = ((hx / (hw + 1e-7) + 1) W - 1) / 2, py likewise with H.  zv [V]; pix_f [V][2] (fp32 pixel position); pix_q [V][2] (int32: px, py times
+ * 2^subpixel_bits, rounded to nearest, ties to even; both INT32_MIN on a marked vertex). */
+int v3d_recon_mesh_project(const float* verts, int32_t num_verts, const v3d_gs_camera* cam, int32_t subpixel_bits, float* zv, float* pix_f,
+                           int32_t* pix_q, v3d_stream_t stream);
+
+/* One thread per face, faces [F][3] (a face with an index outside 0 .. V-1 is not drawn).  A face is drawn when none of its vertices is
+ * marked, its doubled area (int64, of the snapped corners) is not 0, it is a front face or cull = 0, and the bounding box of the pixel centres
+ * it can cover, clamped to the image, is not empty.  tiles_touched [F]: 16 x 16 tiles under that box, 0 for a face that is not drawn;
+ * zmin [F]: the smallest view z of the three vertices. */
+int v3d_recon_mesh_face_setup(const int32_t* faces, int32_t num_faces, const int32_t* pix_q, const float* zv, int32_t num_verts, int32_t width,
+                              int32_t height, int32_t subpixel_bits, int32_t cull, int32_t* tiles_touched, float* zmin, v3d_stream_t stream);
+
+/* keys [n] = tile << 32 | float bits of zmin, vals [n] = face, row-major over the face's tile rectangle, at rows offsets[face] .. (offsets:
+ * exclusive scan of tiles_touched, n its total). */
+int v3d_recon_mesh_duplicate_keys(const int32_t* faces, int32_t num_faces, const int32_t* pix_q, int32_t num_verts, const int32_t* tiles_touched,
+                                  const int32_t* offsets, const float* zmin, int32_t width, int32_t height, int32_t subpixel_bits, uint64_t* keys,
+                                  uint32_t* vals, v3d_stream_t stream);
+
+/* ranges [tiles][2] = [start, end) of every tile in the sorted list, 0 0 for a tile without faces.  num_instances may be 0 (keys_sorted NULL). */
+int v3d_recon_mesh_tile_ranges(const uint64_t* keys_sorted, int32_t num_instances, int32_t width, int32_t height, int32_t* ranges,
+                               v3d_stream_t stream);
+
+/* One 256-thread block per tile, one pixel per thread, 256 faces per LDS batch.  Coverage: the three int64 edge functions at the pixel centre,
+ * with a top-left fill rule where one is 0, applied after orienting the face, so it holds for either winding: two faces that share an edge
+ * cover every pixel centre on it exactly once.  Depth is perspective-correct: b_i = E_i / (E_0 + E_1 + E_2), z = 1 / sum(b_i / zv_i), kept
+ * inside the face's own [zmin, zmax].  The nearest z wins; on bit-equal z the lower face index wins.  The winner is shaded once:
+ * c = z sum(b_i c_i / zv_i) from colors [V][3].
+ * image [3][H][W] (cam->bg where nothing covers), depth [H][W] (view z, 0 where nothing covers), alpha [H][W] (0 or 1), face_id [H][W]
+ * (-1 where nothing covers), n_hit [H][W] (number of drawn faces that cover the pixel centre) or NULL.
+ * The lists are ordered by zmin.  With n_hit NULL a block leaves its list before the first batch whose first zmin lies behind the depth every
+ * one of its pixels already holds (strictly: at equal depth a later face of lower index would still win); with n_hit every list is walked to
+ * its end.  With cull = 0 a closed mesh gives an even n_hit on every pixel.  vals_sorted may be NULL when every range is empty. */
+int v3d_recon_mesh_render(const int32_t* ranges, const uint32_t* vals_sorted, const int32_t* faces, int32_t num_faces, const int32_t* pix_q,
+                          const float* zv, const float* zmin, const float* colors, const v3d_gs_camera* cam, int32_t subpixel_bits, float* image,
+                          float* depth, float* alpha, int32_t* face_id, int32_t* n_hit, v3d_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -4,7 +4,8 @@ checkpoints needed).  Prints one JSON line: total seconds, ms per iteration, Gau
 
     python tools/recon_bench.py [--iterations 4000] [--reso 512] [--mesh 256]
 --mesh N adds the time of the mesh stage on the result (v3d_amd/recon/geometry.py: depth / alpha maps and TSDF fusion of the training views at
-N^3, surface nets, the PLY), second of two runs.
+N^3, surface nets, the PLY), second of two runs, then renders that mesh (v3d_amd/recon/mesh_render.py): rasterization ms per view at 512 x 512 over
+the orbit cameras, and how well the mesh reproduces the training frames (PSNR, coverage, pixels with an odd number of faces over them).
     rocprofv3 --kernel-trace --stats -d /tmp/rp -o rp -- python tools/recon_bench.py --iterations 300     # per-kernel split
 """
 from __future__ import annotations
@@ -66,6 +67,21 @@ def main():
             t3 = time.perf_counter()
         mesh = {"mesh_resolution": a.mesh, "mesh_fuse_ms": round(1000 * (t1 - t0), 2), "mesh_extract_ms": round(1000 * (t2 - t1), 2),
                 "mesh_ply_ms": round(1000 * (t3 - t2), 2), "mesh_vertices": int(verts.shape[0]), "mesh_triangles": int(faces.shape[0])}
+        from v3d_amd.recon import mesh_render as MR
+        if faces.shape[0]:
+            rcams, _ = orbit_cameras(a.views, 2.0, 0.0, 60.0, 512)
+            mv, mf, mc = MR._mesh_on_device(verts, faces, colors, "cuda")          # validated once, outside the timed loop
+            for rep in range(2):      # (second of two runs, as above)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for c in rcams:
+                    MR._render_views(c, mv, mf, mc, [1.0, 1.0, 1.0], ((True, False),))
+                torch.cuda.synchronize()
+                t1 = time.perf_counter()
+            fid = MR.mesh_fidelity(verts, faces, colors, cams, frames, [1.0, 1.0, 1.0])
+            mesh.update({"mesh_render_ms_per_view_512": round(1000 * (t1 - t0) / len(rcams), 3), "mesh_psnr_mean": round(fid["psnr_mean"], 2),
+                         "mesh_psnr_worst": round(min(fid["psnr"]), 2), "mesh_coverage": round(float(np.mean(fid["coverage"])), 4),
+                         "mesh_odd_hit_pixels": int(sum(fid["odd_hit_pixels"]))})
     print(json.dumps({**mesh, "iterations": a.iterations, "reso": a.reso, "views": a.views, "num_pts": a.num_pts, "seconds": round(st["seconds"], 2),
                       "ms_per_iter": round(1000 * st["seconds"] / a.iterations, 3), "num_gaussians": st["num_gaussians"],
                       "psnr_mean": round(float(np.mean(ps)), 2), "device": torch.cuda.get_device_name(0)}))

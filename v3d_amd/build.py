@@ -117,13 +117,14 @@ RECON_LIB = os.path.join(LIBDIR, "libv3d_recon.so")
 
 
 def build_recon(force: bool = False, verbose: bool = True) -> str:
-    """libv3d_recon.so (include/v3d_recon.h): depth / alpha maps, TSDF fusion and surface extraction of the reconstruction step, from
-    csrc_recon/*.hip - its own library, so the kernel library's sources (and the profile that records their hash) stay as they are.  The
+    """libv3d_recon.so (include/v3d_recon.h): depth / alpha maps, TSDF fusion, surface extraction and the mesh rasterizer of the reconstruction
+    step, from csrc_recon/*.hip - its own library, so the kernel library's sources (and the profile that records their hash) stay as they are.  The
     flags of gs.hip, -fno-fast-math included: the maps are held to an fp64 restatement (tests/recon_geom_ref.py)."""
     os.makedirs(LIBDIR, exist_ok=True)
     inc = os.path.join(os.path.dirname(HERE), "include")
     srcs = sorted(os.path.join(RECON_CSRC, f) for f in os.listdir(RECON_CSRC) if f.endswith(".hip"))
     hdrs = [os.path.join(inc, "v3d_recon.h"), os.path.join(inc, "v3d_hip.h")]
+    hdrs += sorted(os.path.join(RECON_CSRC, f) for f in os.listdir(RECON_CSRC) if f.endswith(".h"))
     if force or _stale(RECON_LIB, srcs + hdrs):
         cmd = [_hipcc(), *FLAGS, "-fno-fast-math", "-I", inc, "-shared", *srcs, "-o", RECON_LIB]
         if verbose:

@@ -6,45 +6,12 @@
 // Determinism: no atomics.  A pixel, a voxel, a cell and a grid edge each belong to one thread; compaction goes through exclusive scans.
 // Built without -ffast-math (v3d_amd/build.py): the maps are held to an fp64 restatement (tests/recon_geom_ref.py).
 #include <hip/hip_runtime.h>
-#include <stdarg.h>
 #include <stdint.h>
-#include <stdio.h>
 
+#include "recon_host.h"
 #include "v3d_recon.h"
 
 namespace {
-
-constexpr int TILE = 16;
-constexpr int NT = 256;            // threads per block everywhere (4 waves)
-constexpr int RC_OK = 0, RC_ARG = -1, RC_LAUNCH = -2;
-
-thread_local char g_err[512] = "";
-
-void set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-}
-
-int check_launch(const char* what) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_error("%s: launch failed: %s", what, hipGetErrorString(e));
-        return RC_LAUNCH;
-    }
-    return RC_OK;
-}
-
-#define RECON_REQUIRE(cond, ...)      \
-    do {                              \
-        if (!(cond)) {                \
-            set_error(__VA_ARGS__);   \
-            return RC_ARG;            \
-        }                             \
-    } while (0)
-
-inline unsigned nblk(long long n) { return (unsigned)((n + NT - 1) / NT); }
 
 // ---------------------------------------------------------------------------------------------------------------------------------------
 // Depth / alpha.  The alpha evaluation is the colour pass's (gs.hip splat_alpha), statement for statement: the same skip decisions.
@@ -265,7 +232,7 @@ bool volume_ok(int32_t N) { return N >= 2 && N <= V3D_RECON_MAX_N; }
 #define ST ((hipStream_t)stream)
 
 extern "C" int v3d_recon_abi_version(void) { return V3D_RECON_ABI_VERSION; }
-extern "C" const char* v3d_recon_last_error(void) { return g_err; }
+extern "C" const char* v3d_recon_last_error(void) { return recon_host::g_err; }
 
 extern "C" int v3d_recon_depth_alpha(const int32_t* ranges, const uint32_t* vals_sorted, const float* means2d, const float* conic_opacity,
                                      const float* depth, const int32_t* n_contrib, int32_t width, int32_t height, float* out_depth, float* out_alpha,

@@ -41,6 +41,12 @@ SIGNATURES = {
     "v3d_recon_cells_vertices": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "v3d_recon_edges_flag": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_vp, c_vp]),
     "v3d_recon_edges_faces": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    # mesh rasterizer (csrc_recon/meshrast.hip, v3d_amd/recon/mesh_render.py)
+    "v3d_recon_mesh_project": (c_i32, [c_vp, c_i32, _CAM, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    "v3d_recon_mesh_face_setup": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    "v3d_recon_mesh_duplicate_keys": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    "v3d_recon_mesh_tile_ranges": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
+    "v3d_recon_mesh_render": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, _CAM, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
 }
 
 _lib = None

@@ -1,4 +1,4 @@
-/* v3d_recon.h - C ABI of libv3d_recon.so (v3d_amd/csrc_recon/): geometry from the reconstructed splats.  Forward only; its own
+/* v3d_recon.h - C ABI of libv3d_recon.so (v3d_amd/csrc_recon/): geometry from the reconstructed splats and the refinement of the mesh's colours.  Its own
  * library, beside libv3d_hip.so whose rasterizer intermediates it consumes (include/v3d_hip.h "Gaussian-splat reconstruction").
  *   per view:  v3d_recon_depth_alpha (expected depth + accumulated alpha of every pixel)  ->  v3d_recon_tsdf_integrate (one view into the volume)
  *   once:      v3d_recon_cells_flag -> scan -> v3d_recon_cells_vertices;  v3d_recon_edges_flag -> scan -> v3d_recon_edges_faces
@@ -110,6 +110,52 @@ int v3d_recon_mesh_tile_ranges(const uint64_t* keys_sorted, int32_t num_instance
 int v3d_recon_mesh_render(const int32_t* ranges, const uint32_t* vals_sorted, const int32_t* faces, int32_t num_faces, const int32_t* pix_q,
                           const float* zv, const float* zmin, const float* colors, const v3d_gs_camera* cam, int32_t subpixel_bits, float* image,
                           float* depth, float* alpha, int32_t* face_id, int32_t* n_hit, v3d_stream_t stream);
+
+/* ---- Mesh colour refinement (v3d_amd/csrc_recon/meshshade.hip; host side: v3d_amd/recon/mesh_refine.py) -----------------------------------
+ * Optimises the vertex colours of the mesh against images of known cameras with the geometry held fixed.  What a camera sees then never
+ * changes, so the rasterizer above runs ONCE per view and its result is frozen: the image is a fixed sparse linear map of the colours (three
+ * coefficients per covered pixel, the background elsewhere) and the gradient with respect to the colours is the transpose of that map.
+ *   per view, once:  v3d_recon_mesh_render -> v3d_recon_mesh_pixel_weights -> scan of the coverage -> v3d_recon_mesh_vertex_records -> sort of
+ *                    the records on max(1, bits(V - 1)) key bits -> v3d_recon_mesh_vertex_ranges;  the host then gathers
+ *                    ent_pix [n] = value / 3 and ent_w [n] = depth[pixel] pix_w[value] from the sorted values
+ *   per iteration:   v3d_recon_mesh_shade -> (loss on the host side) -> v3d_recon_mesh_shade_bwd -> v3d_recon_mesh_color_adam
+ * (the scan and the sort are v3d_gs_scan and v3d_gs_radix_sort_pairs of libv3d_hip.so, called by the host).  No atomics: the sort is stable,
+ * so a vertex's entries stay in ascending pixel order, and one wave sums them in an order that the list alone decides.  There is no gradient
+ * through coverage (no silhouette antialiasing): vertex positions are not parameters. */
+
+/* One thread per pixel, on the face_id map of v3d_recon_mesh_render and the pix_q, zv of the same view.  pix_vert [H][W][3]: the three vertex
+ * indices of the winning face, -1 -1 -1 where face_id < 0;  pix_w [H][W][3]: b_k / zv[i_k] with b_k from the int64 edge functions, the
+ * orientation flip and the fp32 quotients of the render kernel, statement for statement; 0 where nothing covers. */
+int v3d_recon_mesh_pixel_weights(const int32_t* face_id, const int32_t* faces, int32_t num_faces, const int32_t* pix_q, const float* zv,
+                                 int32_t num_verts, int32_t width, int32_t height, int32_t subpixel_bits, int32_t* pix_vert, float* pix_w,
+                                 v3d_stream_t stream);
+
+/* One thread per pixel: image [3][H][W], image[ch][p] = depth[p] (w_0 c[i_0][ch] + w_1 c[i_1][ch] + w_2 c[i_2][ch]) from colors [V][3], the
+ * statement the render kernel shades with; bg0 bg1 bg2 where pix_vert is -1.  depth [H][W]: the render's view z. */
+int v3d_recon_mesh_shade(const int32_t* pix_vert, const float* pix_w, const float* depth, const float* colors, int32_t num_verts, int32_t width,
+                         int32_t height, float bg0, float bg1, float bg2, float* image, v3d_stream_t stream);
+
+/* One thread per pixel: three records per covered pixel at rows 3 offsets[pixel] .. + 2 (offsets: exclusive scan of pix_vert[pixel][0] >= 0,
+ * num_records = 3 x its total, positive), keys = vertex index, vals = 3 pixel + k: in pixel order. */
+int v3d_recon_mesh_vertex_records(const int32_t* pix_vert, const int32_t* offsets, int32_t width, int32_t height, int32_t num_records, uint64_t* keys,
+                                  uint32_t* vals, v3d_stream_t stream);
+
+/* ranges [V][2] = [start, end) of every vertex in the sorted records, 0 0 for a vertex without one.  num_records may be 0 (keys_sorted NULL). */
+int v3d_recon_mesh_vertex_ranges(const uint64_t* keys_sorted, int32_t num_records, int32_t num_verts, int32_t* ranges, v3d_stream_t stream);
+
+/* The transpose of the shade: dL_dcolors [V][3] from dL_dimage [3][H][W], dL_dcolors[v][ch] = sum over the entries e of vertex v of
+ * ent_w[e] dL_dimage[ch][ent_pix[e]].  One 64-lane wave per vertex: lane l adds entries start + l, start + l + 64, .. in list order, the
+ * lanes then meet in an xor butterfly, so the result does not depend on the launch shape.  Every row is written, 0 0 0 for a vertex without
+ * entries: the caller need not clear the buffer.  A gradient on an uncovered pixel reaches no vertex.  num_entries may be 0 (ent_pix, ent_w NULL). */
+int v3d_recon_mesh_shade_bwd(const int32_t* ranges, const int32_t* ent_pix, const float* ent_w, int32_t num_entries, const float* dL_dimage,
+                             int32_t width, int32_t height, int32_t num_verts, float* dL_dcolors, v3d_stream_t stream);
+
+/* One thread per element of [V][3], in place on logit, m, v.  grad is dL/dcolors with colors = sigmoid of logit: g = grad s (1 - s), then the
+ * update of torch.optim.Adam (m lerped towards g by 1 - beta1, v = beta2 v + (1 - beta2) g g, bias corrections of `step` = 1, 2, .., eps added
+ * outside the square root, no weight decay), then colors = sigmoid of the new logit.  An element whose grad was 0 on every step so far keeps
+ * its logit bit for bit. */
+int v3d_recon_mesh_color_adam(float* logit, float* m, float* v, const float* grad, int32_t num_verts, double lr, double beta1, double beta2,
+                              double eps, int32_t step, float* colors, v3d_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -2,10 +2,12 @@
 --lambda_lpips 0 --num_pts 100000 -w, 4000 iterations.  The orbit is a seeded 3000-Gaussian scene rendered by the HIP forward (no
 checkpoints needed).  Prints one JSON line: total seconds, ms per iteration, Gaussian count after densification, final training-view PSNR.
 
-    python tools/recon_bench.py [--iterations 4000] [--reso 512] [--mesh 256]
+    python tools/recon_bench.py [--iterations 4000] [--reso 512] [--mesh 256 [--refine 2000]]
 --mesh N adds the time of the mesh stage on the result (v3d_amd/recon/geometry.py: depth / alpha maps and TSDF fusion of the training views at
 N^3, surface nets, the PLY), second of two runs, then renders that mesh (v3d_amd/recon/mesh_render.py): rasterization ms per view at 512 x 512 over
 the orbit cameras, and how well the mesh reproduces the training frames (PSNR, coverage, pixels with an odd number of faces over them).
+--refine ITERS (with --mesh) then refines the mesh's vertex colours against the training frames (v3d_amd/recon/mesh_refine.py, the defaults of
+scripts/pub/refine_mesh.py): ms per iteration, set-up of the optimisation views included, and the mean PSNR over all frames before and after.
     rocprofv3 --kernel-trace --stats -d /tmp/rp -o rp -- python tools/recon_bench.py --iterations 300     # per-kernel split
 """
 from __future__ import annotations
@@ -31,7 +33,10 @@ def main():
     ap.add_argument("--views", type=int, default=18)
     ap.add_argument("--num_pts", type=int, default=100_000)
     ap.add_argument("--mesh", type=int, default=0, metavar="N", help="also time fuse_tsdf + extract_mesh + save_mesh_ply at N^3")
+    ap.add_argument("--refine", type=int, default=0, metavar="ITERS", help="with --mesh: also refine the mesh's vertex colours for ITERS iterations")
     a = ap.parse_args()
+    if a.refine and not a.mesh:
+        ap.error("--refine needs --mesh N")
     import gs_dense_ref as D
     from v3d_amd.recon import rasterize as RZ
     from v3d_amd.recon import train as TR
@@ -82,6 +87,12 @@ def main():
             mesh.update({"mesh_render_ms_per_view_512": round(1000 * (t1 - t0) / len(rcams), 3), "mesh_psnr_mean": round(fid["psnr_mean"], 2),
                          "mesh_psnr_worst": round(min(fid["psnr"]), 2), "mesh_coverage": round(float(np.mean(fid["coverage"])), 4),
                          "mesh_odd_hit_pixels": int(sum(fid["odd_hit_pixels"]))})
+            if a.refine:
+                from v3d_amd.recon import mesh_refine as RFN
+                _, rst = RFN.refine_vertex_colors(verts, faces, colors, cams, frames, iterations=a.refine)
+                mesh.update({"refine_iterations": a.refine, "refine_opt_views": rst["opt_views"],
+                             "refine_ms_per_iter": round(1000 * rst["seconds"] / a.refine, 4), "refine_psnr_before": round(rst["psnr_before"], 2),
+                             "refine_psnr_after": round(rst["psnr_after"], 2)})
     print(json.dumps({**mesh, "iterations": a.iterations, "reso": a.reso, "views": a.views, "num_pts": a.num_pts, "seconds": round(st["seconds"], 2),
                       "ms_per_iter": round(1000 * st["seconds"] / a.iterations, 3), "num_gaussians": st["num_gaussians"],
                       "psnr_mean": round(float(np.mean(ps)), 2), "device": torch.cuda.get_device_name(0)}))

@@ -28,7 +28,7 @@ LIB_PATH = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__
 ABI_VERSION = 1
 MAX_RESOLUTION = 512
 
-c_i32, c_f32, c_vp = C.c_int32, C.c_float, C.c_void_p
+c_i32, c_f32, c_f64, c_vp = C.c_int32, C.c_float, C.c_double, C.c_void_p
 _CAM = C.POINTER(GsCamera)
 
 # name -> (restype, argtypes); must list every symbol declared in include/v3d_recon.h (tests/test_recon_geom_cpu.py)
@@ -47,6 +47,13 @@ SIGNATURES = {
     "v3d_recon_mesh_duplicate_keys": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "v3d_recon_mesh_tile_ranges": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "v3d_recon_mesh_render": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, _CAM, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    # mesh colour refinement (csrc_recon/meshshade.hip, v3d_amd/recon/mesh_refine.py)
+    "v3d_recon_mesh_pixel_weights": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    "v3d_recon_mesh_shade": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_f32, c_f32, c_f32, c_vp, c_vp]),
+    "v3d_recon_mesh_vertex_records": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    "v3d_recon_mesh_vertex_ranges": (c_i32, [c_vp, c_i32, c_i32, c_vp, c_vp]),
+    "v3d_recon_mesh_shade_bwd": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
+    "v3d_recon_mesh_color_adam": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_f64, c_f64, c_f64, c_f64, c_i32, c_vp, c_vp]),
 }
 
 _lib = None

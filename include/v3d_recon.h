@@ -157,6 +157,68 @@ int v3d_recon_mesh_shade_bwd(const int32_t* ranges, const int32_t* ent_pix, cons
 int v3d_recon_mesh_color_adam(float* logit, float* m, float* v, const float* grad, int32_t num_verts, double lr, double beta1, double beta2,
                               double eps, int32_t step, float* colors, v3d_stream_t stream);
 
+/* ---- Mesh topology (v3d_amd/csrc_recon/meshtopo.hip; host side: v3d_amd/recon/mesh_clean.py) ------------------------------------------------
+ * The mesh as a graph: connected components (to drop floaters and vertices that no face uses), Taubin smoothing, vertex normals.  All of it
+ * walks one structure, the list of corners that touch every vertex:
+ *   once:  v3d_recon_mesh_corner_records -> sort of the records on max(1, bits(V - 1)) key bits -> v3d_recon_mesh_vertex_ranges on the sorted
+ *          keys;  ranges [V][2] and corners [3F] = the sorted values.  Corner c = 3 f + k is place k of face f.  The sort is stable, so a
+ *          vertex's corners ascend: that order is the summation order of everything below.
+ *   normals:     v3d_recon_mesh_vertex_normals
+ *   components:  labels = 0 .. V-1, then v3d_recon_mesh_label_round between two buffers until a round changes nothing
+ *   filter:      v3d_recon_mesh_face_labels -> sort on max(1, bits(V)) key bits -> v3d_recon_mesh_vertex_ranges (faces per root) -> the host
+ *                decides which roots stay -> v3d_recon_mesh_keep_flags -> scans of both flag arrays -> v3d_recon_mesh_compact_faces
+ *   smoothing:   v3d_recon_mesh_boundary_flags (optional pins), then v3d_recon_mesh_smooth_pass between two buffers
+ * (the scans and the sorts are v3d_gs_scan and v3d_gs_radix_sort_pairs of libv3d_hip.so, called by the host).  One thread per vertex (or per
+ * face, or per corner); no atomics; bit-reproducible.  V >= 1, F >= 1 and 3 F <= INT32_MAX everywhere: the host handles an empty mesh without
+ * a launch.  A face with an index outside 0 .. V-1 is absent for every entry below, and nothing is read through such an index. */
+
+/* One thread per corner, faces [F][3]: keys [3F] = faces[f][k], vals [3F] = 3 f + k, in corner order.  A key outside 0 .. V-1 is written as 0
+ * so that it stays inside the sorted bits: the entries below skip that corner because its face is absent. */
+int v3d_recon_mesh_corner_records(const int32_t* faces, int32_t num_faces, int32_t num_verts, uint64_t* keys, uint32_t* vals, v3d_stream_t stream);
+
+/* normals [V][3]: the sum over the vertex's list, in list order, of (v1 - v0) x (v2 - v0) of the face (area weighting), divided by its length;
+ * 0 0 1 where the squared length of the sum is not above 1e-20 (no face, no area, or normals that cancel).  verts [V][3]. */
+int v3d_recon_mesh_vertex_normals(const float* verts, int32_t num_verts, const int32_t* faces, int32_t num_faces, const int32_t* ranges,
+                                  const int32_t* corners, float* normals, v3d_stream_t stream);
+
+/* One round of the component labelling, from labels_in [V] to labels_out [V] (two buffers):  m = min(labels_in[v], labels_in of every corner of
+ * every face of v's list),  labels_out[v] = labels_in[m]  (one pointer jump).  Started from labels[v] = v, a label always names a vertex of the
+ * same component with an index <= the vertex's own; the fixed point is the smallest index of the component (a vertex without faces keeps
+ * itself).  Two vertices are joined when a face uses both.  A thread whose label changed stores 1 to changed [1], which the caller cleared;
+ * nothing else is written there.  Plain min-propagation ends within diameter + 1 rounds and the jump only lowers labels: V + 8 rounds without
+ * a fixed point mean broken lists. */
+int v3d_recon_mesh_label_round(const int32_t* faces, int32_t num_faces, const int32_t* ranges, const int32_t* corners, int32_t num_verts,
+                               const int32_t* labels_in, int32_t* labels_out, int32_t* changed, v3d_stream_t stream);
+
+/* One thread per face: keys [F] = labels[faces[f][0]], vals [F] = f, in face order; the key V for an absent face (sort on bits(V) bits:
+ * v3d_recon_mesh_vertex_ranges with V vertices then ignores it).  The ranges of the sorted keys give every root's number of faces. */
+int v3d_recon_mesh_face_labels(const int32_t* faces, int32_t num_faces, const int32_t* labels, int32_t num_verts, uint64_t* keys, uint32_t* vals,
+                               v3d_stream_t stream);
+
+/* keep_root [V]: 1 at the roots (labels at their fixed point) of the components that stay.  keep_face [F] = keep_root[labels[faces[f][0]]];
+ * keep_vert [V] = keep_root[labels[v]] and the vertex has at least one face. */
+int v3d_recon_mesh_keep_flags(const int32_t* faces, int32_t num_faces, const int32_t* ranges, const int32_t* corners, int32_t num_verts,
+                              const int32_t* labels, const int32_t* keep_root, int32_t* keep_face, int32_t* keep_vert, v3d_stream_t stream);
+
+/* One thread per face: faces_out[face_off[f]][k] = vert_off[faces[f][k]] for every kept face (face_off, vert_off: exclusive scans of keep_face
+ * and keep_vert; num_faces_out, num_verts_out their totals, both positive).  The order of faces and of vertices is kept. */
+int v3d_recon_mesh_compact_faces(const int32_t* faces, int32_t num_faces, int32_t num_verts, const int32_t* keep_face, const int32_t* face_off,
+                                 const int32_t* keep_vert, const int32_t* vert_off, int32_t num_faces_out, int32_t num_verts_out, int32_t* faces_out,
+                                 v3d_stream_t stream);
+
+/* flags [V] = 1 where the vertex lies on an open edge.  The entry of v's list at corner k has the two neighbours faces[f][(k + 1) % 3] and
+ * faces[f][(k + 2) % 3]; the flag is set when some neighbour other than v is a neighbour in exactly one entry (on a closed manifold every
+ * neighbour is in two).  Quadratic in the length of the list. */
+int v3d_recon_mesh_boundary_flags(const int32_t* faces, int32_t num_faces, const int32_t* ranges, const int32_t* corners, int32_t num_verts,
+                                  int32_t* flags, v3d_stream_t stream);
+
+/* One pass from verts_in [V][3] to verts_out [V][3] (two buffers):  out = in + factor (mean - in), mean = the sum over v's list, in list
+ * order, of (a + b) / 2 of the entry's two neighbours, divided by the number of entries (the umbrella operator on a closed manifold, where
+ * every neighbour comes twice).  A vertex without faces is copied, and so is one with pinned[v] != 0 (pinned [V] or NULL).  Taubin smoothing
+ * alternates factor = lambda > 0 and factor = mu < -lambda. */
+int v3d_recon_mesh_smooth_pass(const float* verts_in, int32_t num_verts, const int32_t* faces, int32_t num_faces, const int32_t* ranges,
+                               const int32_t* corners, const int32_t* pinned, float factor, float* verts_out, v3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

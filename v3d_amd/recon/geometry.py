@@ -54,6 +54,15 @@ SIGNATURES = {
     "v3d_recon_mesh_vertex_ranges": (c_i32, [c_vp, c_i32, c_i32, c_vp, c_vp]),
     "v3d_recon_mesh_shade_bwd": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "v3d_recon_mesh_color_adam": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_f64, c_f64, c_f64, c_f64, c_i32, c_vp, c_vp]),
+    # mesh topology (csrc_recon/meshtopo.hip, v3d_amd/recon/mesh_clean.py)
+    "v3d_recon_mesh_corner_records": (c_i32, [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    "v3d_recon_mesh_vertex_normals": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    "v3d_recon_mesh_label_round": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    "v3d_recon_mesh_face_labels": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp]),
+    "v3d_recon_mesh_keep_flags": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "v3d_recon_mesh_compact_faces": (c_i32, [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp]),
+    "v3d_recon_mesh_boundary_flags": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp]),
+    "v3d_recon_mesh_smooth_pass": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_f32, c_vp, c_vp]),
 }
 
 _lib = None

@@ -219,6 +219,69 @@ int v3d_recon_mesh_boundary_flags(const int32_t* faces, int32_t num_faces, const
 int v3d_recon_mesh_smooth_pass(const float* verts_in, int32_t num_verts, const int32_t* faces, int32_t num_faces, const int32_t* ranges,
                                const int32_t* corners, const int32_t* pinned, float factor, float* verts_out, v3d_stream_t stream);
 
+/* ---- Mesh decimation (v3d_amd/csrc_recon/meshdecim.hip; host side: v3d_amd/recon/mesh_decimate.py) ----------------------------------------
+ * Quadric-error half-edge collapse in parallel rounds.  The collapse v -> u moves v onto u: u keeps its position (and colour), the two faces on
+ * the edge (v, u) die and v's other faces name u instead.  Vertices are never moved or renumbered here; a dead face holds num_verts in all
+ * three places, which makes it absent for every entry of this header.
+ *   once:       the corner lists (above), then v3d_recon_mesh_vertex_quadrics
+ *   per round:  the corner lists of the live faces: v3d_recon_mesh_corner_records, the sort and v3d_recon_mesh_vertex_ranges called with
+ *               num_verts + 1 vertices (and ranges [V + 1][2]), so that the corners of the dead faces gather on the extra vertex V, which no
+ *               entry below looks at;
+ *               v3d_recon_mesh_decim_propose -> v3d_recon_mesh_decim_min_round twice (keys -> min1 -> min2) -> v3d_recon_mesh_decim_accept ->
+ *               sort of (sel_keys, sel_vals) on 64 bits -> v3d_recon_mesh_decim_cut -> v3d_recon_mesh_decim_apply -> scan of `live`, whose
+ *               total is the next round's live_faces
+ *   at the end: v3d_recon_mesh_compact_faces with keep_face = live and keep_vert = 1 - removed
+ * (the scans and the sorts are v3d_gs_scan and v3d_gs_radix_sort_pairs of libv3d_hip.so, called by the host, which reads the totals and the
+ * flags back once per group of rounds).  One thread per vertex (or per face); no atomics; bit-reproducible.  Positions are fp32; quadrics,
+ * costs and the normal test are fp64.  V >= 1, F >= 1 and 3 F <= INT32_MAX everywhere.  The valence of a vertex is the number of its faces. */
+#define V3D_RECON_MESH_MAX_VALENCE 1024
+
+/* quadrics [V][10] (fp64): the sum over the vertex's list, in list order, of w (a b c d)^T (a b c d), upper triangle row by row (aa ab ac ad bb
+ * bc bd cc cd dd), of every face with area: n = (v1 - v0) x (v2 - v0), (a b c) = n / |n|, d = -(a b c) . v0, w = |n| / 2.  Zeros without a face. */
+int v3d_recon_mesh_vertex_quadrics(const float* verts, int32_t num_verts, const int32_t* faces, int32_t num_faces, const int32_t* ranges,
+                                   const int32_t* corners, double* quadrics, v3d_stream_t stream);
+
+/* One thread per vertex: keys [V], targets [V].  v is removable when it has 3 .. max_valence faces and they form one closed fan (every
+ * neighbour follows v in exactly one of them and precedes it in exactly one, and walking from face to face comes round after all of them):
+ * a vertex on an open edge, a non-manifold one, one without faces and one above the cap propose nothing.  v -> u for a neighbour u is valid when
+ *   - the faces (v, u, a1) and (v, a2, u) on the edge have a1 != a2 and no other neighbour of v is a neighbour of u (the link condition),
+ *   - u would end with at most max_valence faces (it has n_u + n_v - 4 afterwards),
+ *   - every face of v without u keeps n_before . n_after > 0 for n = (v1 - v0) x (v2 - v0) before and after v is replaced by u's position
+ *     (no flip, no face without area before or after),
+ *   - no face of v without u would repeat the three vertices of a face u already has.
+ * cost = p^T (Q_v + Q_u) p at u's position p (homogeneous), clamped at 0, rounded to fp32; a cost that is not a number is no candidate.
+ * targets[v] = the valid u of the smallest fp32 cost, the smaller u among equals; keys[v] = fp32 bits of that cost << 32 | v.  Without a valid
+ * neighbour keys[v] is all ones and targets[v] = -1. */
+int v3d_recon_mesh_decim_propose(const float* verts, int32_t num_verts, const int32_t* faces, int32_t num_faces, const int32_t* ranges,
+                                 const int32_t* corners, const double* quadrics, int32_t max_valence, uint64_t* keys, int32_t* targets,
+                                 v3d_stream_t stream);
+
+/* keys_out [V] = the smallest of keys_in over v and every corner of every face of v's list (two buffers).  Twice: the smallest key within
+ * graph distance 2. */
+int v3d_recon_mesh_decim_min_round(const int32_t* faces, int32_t num_faces, const int32_t* ranges, const int32_t* corners, int32_t num_verts,
+                                   const uint64_t* keys_in, uint64_t* keys_out, v3d_stream_t stream);
+
+/* One thread per vertex: v is a local minimum when keys[v] is not all ones and equals min2[v]; accept [V] = 1 for the local minima whose cost
+ * is at most max_error (>= 0, +inf for no limit), else 0.  Keys are distinct, so two accepted vertices are at least 3 edges apart: no face
+ * holds two, no two share a target, no target is accepted or next to another accepted vertex.  sel_keys [V] = keys[v] where accepted, all ones
+ * elsewhere; sel_vals [V] = v.  flags [2], cleared by the caller: flags[0] = 1 when there is a local minimum, flags[1] = 1 when one is accepted
+ * (the smallest key of the mesh always is a local minimum: flags[0] set with flags[1] clear means that it costs more than max_error). */
+int v3d_recon_mesh_decim_accept(const uint64_t* keys, const uint64_t* min2, int32_t num_verts, float max_error, int32_t* accept, uint64_t* sel_keys,
+                                uint32_t* sel_vals, int32_t* flags, v3d_stream_t stream);
+
+/* One thread per row of the sorted (sel_keys, sel_vals): every collapse removes two faces, so only the ceil((live_faces[0] - target_faces) / 2)
+ * accepted vertices of the smallest keys stay accepted (none when live_faces[0] <= target_faces); accept of the others is cleared.  live_faces
+ * is a DEVICE pointer to the number of live faces. */
+int v3d_recon_mesh_decim_cut(const uint64_t* sel_keys_sorted, const uint32_t* sel_vals_sorted, int32_t num_verts, const int32_t* live_faces,
+                             int32_t target_faces, int32_t* accept, v3d_stream_t stream);
+
+/* Thread t decides face t and vertex t.  faces_out [F][3] (two buffers): a face with an accepted corner v and targets[v] dies (V V V), one with
+ * v alone names targets[v] in v's place, every other face is copied; an absent face becomes a dead one.  live [F] = 1 for the faces that
+ * remain.  For every accepted v: quadrics[targets[v]] += quadrics[v] in place (one writer per row, and no row that is read is written) and
+ * removed[v] = 1; removed is otherwise left as it is. */
+int v3d_recon_mesh_decim_apply(const int32_t* faces_in, int32_t num_faces, int32_t num_verts, const int32_t* accept, const int32_t* targets,
+                               int32_t* faces_out, int32_t* live, double* quadrics, int32_t* removed, v3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -63,6 +63,12 @@ SIGNATURES = {
     "v3d_recon_mesh_compact_faces": (c_i32, [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp]),
     "v3d_recon_mesh_boundary_flags": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp]),
     "v3d_recon_mesh_smooth_pass": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_f32, c_vp, c_vp]),
+    "v3d_recon_mesh_vertex_quadrics": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    "v3d_recon_mesh_decim_propose": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp]),
+    "v3d_recon_mesh_decim_min_round": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp]),
+    "v3d_recon_mesh_decim_accept": (c_i32, [c_vp, c_vp, c_i32, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "v3d_recon_mesh_decim_cut": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp]),
+    "v3d_recon_mesh_decim_apply": (c_i32, [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
 }
 
 _lib = None

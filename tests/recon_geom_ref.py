@@ -94,7 +94,8 @@ def tsdf_view(vol, depth, alpha, image, cam, alpha_min=ALPHA_MIN):
 
 # fp32 against fp64 in tsdf_integrate_kernel.  A voxel's continuous pixel coordinate is W / 2 times a quotient of two 4-term dot products of
 # magnitude <= 4: each carries at most 4 roundings of 2^-24 relative to ~4, the quotient and the affine map three more; at W = 32 that is below
-# 16 * 12 * 6e-8 * 4 = 5e-5 pixels.  PIXEL_MARGIN is 4x that.  View z and depth / alpha (values ~2, ulp 2.4e-7) carry at most 6 roundings between
+# 16 * 12 * 6e-8 * 4 = 5e-5 pixels.  PIXEL_MARGIN is 4x that (2x at W = 56, the widest of TSDF_CASES; tests/test_recon_geom_cpu.py holds
+# that the float32 run decides every voxel outside the margins as the fp64 run does, case by case).  View z and depth / alpha (values ~2, ulp 2.4e-7) carry at most 6 roundings between
 # them: 1.5e-6; SDF_MARGIN (on |sdf| against trunc and on z against 0.2) is ~7x that.  alpha is read, not computed: any distance from alpha_min
 # that fp32 can represent decides the same, the margin only keeps the test scenes from sitting on the threshold.  A mean TSDF is a sum of at
 # most 8 terms of size <= 1 divided by a small integer, each term off by SDF_MARGIN / trunc at most: SIGN_MARGIN bounds that for trunc >= 0.1.
@@ -215,6 +216,71 @@ def sphere_volume(N, bound, radius, dtype=torch.float32):
     return vol
 
 
+def random_volume(N, seed, p_unseen=0.03, bound=1.0):
+    """A float32 volume of independent voxels: weight an integer in 1 .. 4, 0 (unobserved) with probability p_unseen; mean TSDF uniform in
+    -1 .. 1; colour weight an integer in 0 .. 2, 0 on the block [: N // 2, : N // 2, :]; mean colour uniform in 0 .. 1.  Its cells take
+    nearly every configuration of corner signs, some have an unobserved corner, some no coloured corner."""
+    g = torch.Generator().manual_seed(seed)
+    vol = new_volume(N, bound, dtype=torch.float32)
+    w = torch.randint(1, 5, (N ** 3,), generator=g).float()
+    w[torch.rand(N ** 3, generator=g) < p_unseen] = 0
+    vol["weight"] = w
+    vol["tsdf_sum"] = (torch.rand(N ** 3, generator=g) * 2 - 1) * w
+    rw = torch.randint(0, 3, (N, N, N), generator=g).float()
+    rw[:N // 2, :N // 2, :] = 0
+    vol["rgb_weight"] = rw.reshape(-1)
+    vol["rgb_sum"] = torch.rand(3, N ** 3, generator=g) * vol["rgb_weight"]
+    return vol
+
+
+def plane_volume(N, normal, offset, bound=1.0):
+    """A float32 volume holding the signed distance to the plane normal . p = offset (normal normalised; in units of trunc, clamped at +-1;
+    negative below the plane), weight and colour weight 1 everywhere, coloured by position."""
+    vol = new_volume(N, bound, dtype=torch.float32)
+    p = voxel_centres(N, bound)
+    n = torch.tensor(normal, dtype=torch.float64)
+    vol["tsdf_sum"] = ((p @ (n / n.norm()) - offset) / vol["trunc"]).clamp(-1, 1).float()
+    vol["weight"] = torch.ones(N ** 3)
+    vol["rgb_sum"] = (0.5 + 0.5 * p.t() / bound).clamp(0, 1).float().contiguous()
+    vol["rgb_weight"] = torch.ones(N ** 3)
+    return vol
+
+
+# The volumes of the surface-nets tests beside the sphere: name -> builder.  tests/test_recon_geom_cpu.py states what each one covers.
+MESH_VOLUMES = {
+    "random13": lambda: random_volume(13, 2),          # 13^3, 12^3 and 3 * 13^3 all end in a partial block of 256
+    "random11": lambda: random_volume(11, 1),
+    "random6": lambda: random_volume(6, 3),
+    "random3": lambda: random_volume(3, 5),
+    "random2": lambda: random_volume(2, 4),            # one cell
+    "plane-oblique": lambda: plane_volume(13, (0.3, 0.5, 0.81), 0.05),
+    "plane-x": lambda: plane_volume(12, (1, 0, 0), 0.0),
+    "plane-z-zero": lambda: plane_volume(13, (0, 0, 1), 0.0),      # a layer of voxels whose mean is exactly 0, above the negative side
+    "plane-z-zero-down": lambda: plane_volume(13, (0, 0, -1), 0.0),    # ... and below it
+}
+
+
+def promoted(vol):
+    """The same volume with its tensors in fp64"""
+    return {k: (v.double() if torch.is_tensor(v) else v) for k, v in vol.items()}
+
+
+def cell_stats(vol):
+    """Of a volume's (N-1)^3 cells: `configurations`, the distinct mixed corner-sign patterns (8 bits, neither 0 nor 255) among the cells with all
+    corners observed, and `refused_unseen`, the number of cells with an unobserved corner whose observed corners change sign."""
+    N = vol["N"]
+    M = N - 1
+    w = vol["weight"].reshape(N, N, N)
+    neg = (w > 0) & (vol["tsdf_sum"].reshape(N, N, N) < 0)        # the sign of a mean is the sign of its numerator
+    corner = lambda t, k: t[(k >> 2) & 1:M + ((k >> 2) & 1), (k >> 1) & 1:M + ((k >> 1) & 1), (k & 1):M + (k & 1)]  # noqa: E731
+    seen = torch.stack([corner(w, k) > 0 for k in range(8)])
+    negs = torch.stack([corner(neg, k) for k in range(8)])
+    code = sum(negs[k].long() << k for k in range(8))
+    mixed = seen.all(0) & (code > 0) & (code < 255)
+    pos = (seen & ~negs).any(0)
+    return dict(configurations=int(torch.unique(code[mixed]).numel()), refused_unseen=int((~seen.all(0) & negs.any(0) & pos).sum()))
+
+
 # ---- mesh measures ------------------------------------------------------------------------------------------------------------------
 def edge_table(faces):
     """directed edges [3F, 2] of a triangle list (numpy int64)"""
@@ -247,6 +313,14 @@ def chamfer(a, b):
 # measured on the CPU (e2e_restatement(torch.float32) vs e2e_restatement()): 3.21e-8 at 2694 vertices each.  It is what the number format
 # costs; the kernels are granted 4x that (tests/test_recon_geom_gpu.py).
 E2E_CHAMFER_FP32 = 3.21e-8
+# The same measure for the ragged end-to-end case E2E_RAGGED below (72 x 40 views, a 30^3 volume whose last block of voxels is partial), again
+# from the restatement alone on the CPU, with tests/ and the repository root on sys.path:
+#   python -c "import torch, recon_geom_ref as R; a = R.e2e_restatement(torch.float32, **R.E2E_RAGGED); b = R.e2e_restatement(**R.E2E_RAGGED);
+#   print(a[0].shape, a[1].shape, b[0].shape, b[1].shape, R.chamfer(a[0], b[0]))"
+# 2.21e-6 at 2293 vertices and 4472 triangles on both sides, the same faces.  (70x the square case's: the median vertex moves by 5e-8 as there,
+# but 65 move by more than 1e-6, up to 5e-4: a few voxel-views that float32 decides the other way, without a change of sign.  N and the scene
+# seed are the first ones tried.)
+E2E_CHAMFER_FP32_RAGGED = 2.21e-6
 
 
 # ---- the end-to-end scene -----------------------------------------------------------------------------------------------------------
@@ -266,8 +340,11 @@ def shell_scene(n=E2E["n"], radius=E2E["radius"], seed=E2E["seed"]):
     return [t.float() for t in (p, scale, rot, op, fdc.view(n, 1, 3))]
 
 
-def e2e_cameras():
-    return D.cams_for(E2E["size"], E2E["size"], n=E2E["views"], elevation=20.0)
+E2E_RAGGED = dict(W=72, H=40, N=30)      # 30^3 = 105 * 256 + 120
+
+
+def e2e_cameras(W=None, H=None):
+    return D.cams_for(E2E["size"] if W is None else W, E2E["size"] if H is None else H, n=E2E["views"], elevation=20.0)
 
 
 E2E_BOUND = 0.75        # fixed for both sides of the comparison (fuse_tsdf's default would come from fp32 positions)
@@ -278,41 +355,98 @@ def cam_to(cam, device):
     return dataclasses.replace(cam, world_view=cam.world_view.to(device), full_proj=cam.full_proj.to(device), center=cam.center.to(device))
 
 
-def e2e_restatement(dtype=torch.float64, bg=(1.0, 1.0, 1.0), device="cpu"):
+def e2e_restatement(dtype=torch.float64, bg=(1.0, 1.0, 1.0), device="cpu", W=None, H=None, N=None):
     """The end-to-end scene through the restatement alone, every step in `dtype`: vertices [V, 3], faces, colours (on the CPU).  `device`: where
-    the torch statements run (the restatement creates its tensors on torch's default device, set here)."""
-    S = E2E["size"]
+    the torch statements run (the restatement creates its tensors on torch's default device, set here).  W x H views (E2E["size"] squared by
+    default) into an N^3 volume (E2E["N"])."""
+    W, H = E2E["size"] if W is None else W, E2E["size"] if H is None else H
     scene = [t.to(device) for t in shell_scene()]
     with torch.device(device):
-        vol = new_volume(E2E["N"], E2E_BOUND, dtype=dtype)
-        for cam in e2e_cameras():
+        vol = new_volume(E2E["N"] if N is None else N, E2E_BOUND, dtype=dtype)
+        for cam in e2e_cameras(W, H):
             cam = cam_to(cam, device)
-            da = depth_alpha(scene, cam, S, S, dtype)
-            tsdf_view(vol, da["depth"], da["alpha"], image_of(da, bg, S, S), cam)
+            da = depth_alpha(scene, cam, W, H, dtype)
+            tsdf_view(vol, da["depth"], da["alpha"], image_of(da, bg, W, H), cam)
         return tuple(t.cpu() for t in extract(vol)[:3])
 
 
-def sphere_tsdf_case(N=24, size=32, views=4, radius=0.5, bound=1.0):
-    """The TSDF test's inputs: cameras and closed-form float32 maps of `views` orbit views of a sphere"""
-    cams = D.cams_for(size, size, n=views, elevation=15.0)
-    return dict(N=N, bound=bound, cams=cams, maps=[sphere_view(c, radius) for c in cams])
+def sphere_tsdf_case(N=24, size=32, views=4, radius=0.5, bound=1.0, W=None, H=None, elevation=15.0, trunc=None, alpha_min=ALPHA_MIN):
+    """The TSDF test's inputs: cameras and closed-form float32 maps of `views` orbit views (W x H, `size` squared by default) of a sphere"""
+    cams = D.cams_for(size if W is None else W, size if H is None else H, n=views, elevation=elevation)
+    return dict(N=N, bound=bound, trunc=trunc, alpha_min=alpha_min, cams=cams, maps=[sphere_view(c, radius) for c in cams])
+
+
+# The default case and four with a partial last block of voxels (N^3 mod 256 = 168, 168, 152, 200), landscape and portrait views, cameras
+# inside the volume (bound 2.25 > their distance 2: voxels at view z <= 0.2 and behind the camera), explicit trunc and alpha_min.
+# Even N only: with odd N the centre plane of voxels projects exactly onto pixel-rounding boundaries of an even-sized image, and 4-6 % of the
+# volume lands inside PIXEL_MARGIN (checked at N = 25 and N = 17).
+_RAGGED = dict(radius=0.9, bound=2.25, trunc=0.4)
+TSDF_CASES = {
+    "default": dict(),
+    "n26-40x24": dict(N=26, W=40, H=24, views=5, elevation=15.0, alpha_min=0.5, **_RAGGED),
+    "n26-24x40": dict(N=26, W=24, H=40, views=5, elevation=-20.0, alpha_min=0.3, **_RAGGED),
+    "n22-24x40": dict(N=22, W=24, H=40, views=4, elevation=-20.0, alpha_min=0.3, **_RAGGED),
+    "n18-56x40": dict(N=18, W=56, H=40, views=3, elevation=15.0, alpha_min=0.5, **_RAGGED),
+}
+TSDF_CANARY_CASE = "n26-24x40"      # (the first voxel past this volume lies inside one of its views: tsdf_phantom_voxel)
+
+
+def sphere_tsdf_views(case, dtype=torch.float64):
+    """(volume, what tsdf_view returned per view) of a sphere_tsdf_case"""
+    vol = new_volume(case["N"], case["bound"], case["trunc"], dtype=dtype)
+    return vol, [tsdf_view(vol, d, a, img, cam, case["alpha_min"]) for cam, (d, a, img) in zip(case["cams"], case["maps"])]
 
 
 def sphere_tsdf_restatement(case, dtype=torch.float64):
     """(volume, margin voxels [N^3] bool) of sphere_tsdf_case through tsdf_view"""
-    vol = new_volume(case["N"], case["bound"], dtype=dtype)
-    views = [tsdf_view(vol, d, a, img, cam) for cam, (d, a, img) in zip(case["cams"], case["maps"])]
-    near = tsdf_margins(views, vol["trunc"])
+    vol, views = sphere_tsdf_views(case, dtype)
+    near = tsdf_margins(views, vol["trunc"], case["alpha_min"])
     near |= (vol["weight"] > 0) & ((vol["tsdf_sum"] / vol["weight"].clamp_min(1)).abs() < SIGN_MARGIN)     # sign of the mean TSDF
     return vol, near
 
 
+def tsdf_branch_counts(vol, views):
+    """How often the restatement leaves tsdf_integrate_kernel by each of its ways, summed over the views (voxel-views), and the number of
+    voxels no view wrote."""
+    trunc = vol["trunc"]
+    n = lambda f: sum(int(f(v).sum()) for v in views)  # noqa: E731
+    surf = lambda v: v["seen"] & ~v["empty"]  # noqa: E731
+    return dict(near_plane=n(lambda v: ~v["front"]), off_image=n(lambda v: v["front"] & ~v["seen"]), empty=n(lambda v: v["empty"]),
+                behind=n(lambda v: surf(v) & (v["sdf"] < -trunc)), clamped=n(lambda v: surf(v) & (v["sdf"] > trunc)),
+                colour=n(lambda v: surf(v) & (v["sdf"].abs() <= trunc)), unseen=int((vol["weight"] == 0).sum()))
+
+
+def tsdf_phantom_voxel(case):
+    """What tsdf_integrate_kernel would do with linear index N^3, the first past the volume (ix = iy = 0, iz = N), were its bound check off by
+    one: the number of views of `case` that write it (fp64 statements of tsdf_view).  tests/test_recon_geom_cpu.py holds this above 0 for the
+    case whose accumulators the GPU test surrounds with guard elements."""
+    N, bound = case["N"], case["bound"]
+    trunc = 4.0 * 2.0 * bound / N if case["trunc"] is None else case["trunc"]
+    c = lambda i: (i + 0.5) * (2.0 * bound / N) - bound  # noqa: E731
+    ph = torch.tensor([c(0), c(0), c(N), 1.0], dtype=torch.float64)
+    written = 0
+    for cam, (depth, alpha, _) in zip(case["cams"], case["maps"]):
+        W, H = cam.width, cam.height
+        zv = float((ph @ cam.world_view.double())[2])
+        hom = ph @ cam.full_proj.double()
+        pw = 1.0 / (float(hom[3]) + 1e-7)
+        rx = np.floor(((float(hom[0]) * pw + 1) * W - 1) * 0.5 + 0.5)
+        ry = np.floor(((float(hom[1]) * pw + 1) * H - 1) * 0.5 + 0.5)
+        if not (zv > 0.2 and 0 <= rx < W and 0 <= ry < H):
+            continue
+        a, dm = float(alpha[int(ry), int(rx)]), float(depth[int(ry), int(rx)])
+        written += int(a < case["alpha_min"] or not a > 0 or dm / a - zv >= -trunc)
+    return written
+
+
 # ---- depth / alpha cases ------------------------------------------------------------------------------------------------------------
 # (kind, seed, W, H, view of cams_for): random_scene(300, seed) of gs_dense_ref.SCENE_SEEDS at 64 x 48 and at the ragged 56 x 40, two views
-# each, and one deep_scene(1200) case of gs_dense_ref.EDGE_CASES (tile lists of several batches, saturated pixels, early stop).  Every fp64
-# decision of every case keeps gs_dense_ref.SCENE_MARGIN (tests/test_recon_geom_cpu.py).
+# each, one deep_scene(1200) case of gs_dense_ref.EDGE_CASES (tile lists of several batches, saturated pixels, early stop), and portrait
+# images: 40 x 56, 24 x 72 and 8 x 24, the last narrower than one 16-pixel tile (a single column of tiles).  Every fp64 decision of every
+# case keeps gs_dense_ref.SCENE_MARGIN (tests/test_recon_geom_cpu.py); (seed, view) pairs that do not on a portrait image are left out.
 DEPTH_CASES = tuple(("random", seed, W, H, view) for seed in D.SCENE_SEEDS for W, H in ((64, 48), (56, 40)) for view in (0, 2)) + \
-    (("deep", 73, 56, 40, 2),)
+    (("deep", 73, 56, 40, 2),) + \
+    (("random", 1116, 40, 56, 1), ("random", 2270, 40, 56, 3), ("random", 1116, 24, 72, 1), ("random", 2270, 24, 72, 3), ("random", 1116, 8, 24, 1))
 
 
 def depth_case(case):

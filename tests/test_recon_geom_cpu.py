@@ -174,16 +174,25 @@ def test_deep_depth_case_covers_batches_saturation_and_early_stop():
     assert float((da["final_T"] - pr["final_T"]).abs().max()) <= 1e-12
 
 
-def test_tsdf_scene_keeps_its_margins():
+@pytest.mark.parametrize("name", list(R.TSDF_CASES))
+def test_tsdf_scene_keeps_its_margins(name):
     """Nearest-pixel rounding, z against 0.2, |sdf| against trunc, alpha against alpha_min and the sign of the mean TSDF are not decided
     within fp32 error outside the excluded voxels, and those are at most 1 % of the volume: the float32 run of the restatement then makes
-    every decision as the fp64 run does."""
-    case = R.sphere_tsdf_case()
+    every decision as the fp64 run does.  Every case but the default also leaves the kernel by each of its ways (the default never by z <= 0.2)."""
+    case = R.sphere_tsdf_case(**R.TSDF_CASES[name])
     vol, near = R.sphere_tsdf_restatement(case)
     share = float(near.double().mean())
     print(f"excluded share {share:.4%}")
     assert share <= R.MAX_EXCLUDED, share
-    assert float((vol["weight"] > 0).double().mean()) > 0.9 and vol["weight"].max() == len(case["cams"])
+    counts = R.tsdf_branch_counts(*R.sphere_tsdf_views(case))
+    print(counts)
+    if name == "default":
+        assert float((vol["weight"] > 0).double().mean()) > 0.9 and vol["weight"].max() == len(case["cams"])
+        assert counts["near_plane"] == 0 and min(v for k, v in counts.items() if k != "near_plane") > 0
+    else:
+        assert case["N"] ** 3 % 256 != 0 and case["cams"][0].width != case["cams"][0].height
+        assert min(counts.values()) > 0, counts
+        assert vol["trunc"] == 0.4 != 4 * 2 * case["bound"] / case["N"]
     inside = (vol["weight"] > 0) & (vol["tsdf_sum"] < 0)
     assert 50 < int(inside.sum()) < case["N"] ** 3 // 8                         # a surface: some voxels inside, most outside
     vol32, _ = R.sphere_tsdf_restatement(case, torch.float32)
@@ -195,3 +204,111 @@ def test_tsdf_scene_keeps_its_margins():
     print(f"float32 restatement vs fp64, mean TSDF: {err:.3e}")
     assert err <= 1e-5 / 4          # the GPU bar is 1e-5: the number format alone stays well inside it
     assert bool(((mean32 < 0) == (mean64 < 0))[keep].all())
+
+
+def test_tsdf_canary_case_would_write_the_first_voxel_past_the_volume():
+    # tests/test_recon_geom_gpu.py surrounds this case's accumulators with guard elements: a bound check that let linear index N^3 through
+    # would have to write there for the guards to notice, and some view does (another case's views all miss that voxel)
+    case = R.sphere_tsdf_case(**R.TSDF_CASES[R.TSDF_CANARY_CASE])
+    assert case["N"] ** 3 % 256 not in (0, 255) and R.tsdf_phantom_voxel(case) > 0
+    assert R.tsdf_phantom_voxel(R.sphere_tsdf_case(**R.TSDF_CASES["n26-40x24"])) == 0
+
+
+# ---- the volumes of the surface-nets tests ----------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def meshes():
+    """name -> (volume, restatement's extraction of its float32 values promoted to fp64)"""
+    vols = {name: make() for name, make in R.MESH_VOLUMES.items()}
+    return {name: (vol, R.extract(R.promoted(vol))) for name, vol in vols.items()}
+
+
+@pytest.mark.parametrize("name", list(R.MESH_VOLUMES))
+def test_float32_restatement_extracts_the_same_mesh(meshes, name):
+    # every decision of the extraction is the sign of a numerator or a weight against 0: exact in any format.  What is left is the arithmetic
+    # of the vertex positions and colours, a few ulp of 1 (the GPU bar is 1e-6)
+    vol, (rv, rf, rc, _, _) = meshes[name]
+    v32, f32, c32, _, _ = R.extract(vol)
+    assert v32.dtype == torch.float32 and rv.dtype == torch.float64 and rv.shape[0] > 0
+    assert torch.equal(f32, rf) and v32.shape == rv.shape
+    assert float((v32.double() - rv).abs().max()) <= 2.5e-7 and float((c32.double() - rc).abs().max()) <= 2.5e-7
+
+
+@pytest.mark.parametrize("name, vertices, faces, configurations", [("random13", 1298, 2282, 253), ("random11", 808, 1558, 246)])
+def test_random_volumes_cover_the_sign_configurations(meshes, name, vertices, faces, configurations):
+    vol, (rv, rf, rc, flags, _) = meshes[name]
+    N = vol["N"]
+    assert N ** 3 % 256 and (N - 1) ** 3 % 256 and 3 * N ** 3 % 256           # every launch ends in a partial block
+    stats = R.cell_stats(vol)
+    grey = int((rc == 0.5).all(1).sum())
+    print(stats, f"{grey} grey vertices of {rv.shape[0]}, {rf.shape[0]} faces")
+    assert stats["configurations"] == configurations >= 246                   # of the 254 mixed ones
+    assert stats["refused_unseen"] > 100
+    assert grey > 100
+    assert bool(((rc >= 0) & (rc <= 1)).all()) and int((rc != 0.5).any(1).sum()) > 100
+    assert (rv.shape[0], rf.shape[0]) == (vertices, faces) and int(flags.sum()) == vertices
+    assert 0 <= int(rf.min()) and int(rf.max()) < vertices
+
+
+def test_tiny_random_volumes(meshes):
+    for name in ("random6", "random3"):
+        vol, (rv, rf, _, flags, _) = meshes[name]
+        N = vol["N"]
+        M = N - 1
+        assert rv.shape[0] > 0 and rf.shape[0] > 0
+        cells = torch.nonzero(flags).reshape(-1)
+        idx = torch.stack([cells % M, (cells // M) % M, cells // (M * M)], 1)
+        if N == 3:
+            assert bool(((idx == 0) | (idx == M - 1)).any(1).all())            # every flagged cell touches the border
+    vol, (rv, rf, _, flags, _) = meshes["random2"]
+    assert rv.shape == (1, 3) and rf.shape == (0, 3) and int(flags.sum()) == 1     # one cell: a vertex and no interior edge
+
+
+def test_oblique_plane_runs_into_every_face_of_the_volume(meshes):
+    vol, (rv, rf, _, _, _) = meshes["plane-oblique"]
+    N, bound = vol["N"], vol["bound"]
+    voxel = 2 * bound / N
+    for d in range(3):          # vertices in the first and in the last layer of cells along every axis
+        assert float(rv[:, d].min()) < -bound + 1.5 * voxel and float(rv[:, d].max()) > bound - 1.5 * voxel
+    # sign-changing grid edges on the border, which edge_cells has to refuse: the restatement's faces hold none of them
+    neg = (vol["tsdf_sum"] < 0).reshape(N, N, N)
+    border = 0
+    for axis in range(3):       # (tensor dimension 2 - axis)
+        a, b = neg.narrow(2 - axis, 0, N - 1), neg.narrow(2 - axis, 1, N - 1)
+        cross = a != b
+        for other in range(3):
+            if other != axis:
+                border += int(cross.select(2 - other, 0).sum()) + int(cross.select(2 - other, N - 1).sum())
+    assert border > 50, border
+    _, cnt, dirsum = R.undirected_counts(rf.numpy())
+    assert (cnt <= 2).all() and int((cnt == 1).sum()) > 0 and (dirsum[cnt == 2] == 0).all()
+    assert (rv.shape[0], rf.shape[0]) == (285, 502)
+    n = torch.tensor([0.3, 0.5, 0.81], dtype=torch.float64)
+    assert float((rv @ (n / n.norm()) - 0.05).abs().max()) <= 1e-6              # linear interpolation of a linear field: on the plane
+
+
+def test_axis_plane_between_two_layers_of_voxels(meshes):
+    vol, (rv, rf, _, _, _) = meshes["plane-x"]
+    M = vol["N"] - 1
+    assert rv.shape[0] == M * M == 121 and rf.shape[0] == 2 * (M - 1) ** 2 == 200
+    assert float(rv[:, 0].abs().max()) <= 1e-6
+    _, cnt, dirsum = R.undirected_counts(rf.numpy())
+    assert (cnt <= 2).all() and (dirsum[cnt == 2] == 0).all() and int((cnt == 1).sum()) == 4 * (M - 1)
+    v = rv[rf]
+    normal = torch.linalg.cross(v[:, 1] - v[:, 0], v[:, 2] - v[:, 0])
+    assert bool((normal[:, 0] > 0).all())                                       # from the negative side (x < 0) to the positive one
+
+
+@pytest.mark.parametrize("name, up", [("plane-z-zero", 1.0), ("plane-z-zero-down", -1.0)])
+def test_a_mean_of_exactly_zero_counts_as_outside(meshes, name, up):
+    """13 voxels a side: the middle layer has z = 0 and a mean TSDF of exactly 0, which is not < 0.  The surface then lies between that layer
+    and the negative one beside it, and every crossing interpolates to the zero layer itself: s = m0 / (m0 - 0) = 1 from below (normal
+    +z), s = 0 / (0 - m1) = 0 from above (normal -z).  The vertices are at z = 0 (the restatement gives 1.2e-16 and 0)."""
+    vol, (rv, rf, _, _, mean) = meshes[name]
+    N = vol["N"]
+    M = N - 1
+    assert int((mean == 0).sum()) == N * N == 169 and bool((mean.reshape(N, N, N)[N // 2] == 0).all())
+    assert rv.shape[0] == M * M == 144 and rf.shape[0] == 2 * (M - 1) ** 2 == 242
+    assert float(rv[:, 2].abs().max()) <= 1e-6
+    v = rv[rf]
+    normal = torch.linalg.cross(v[:, 1] - v[:, 0], v[:, 2] - v[:, 0])
+    assert bool((normal[:, 2] * up > 0).all())

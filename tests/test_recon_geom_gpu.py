@@ -1,7 +1,11 @@
 """Geometry from the splats on the gfx950 kernels of libv3d_recon.so (csrc_recon/geom.hip, v3d_amd/recon/geometry.py) against the torch
 restatement (tests/recon_geom_ref.py): depth and alpha maps, TSDF integration, surface nets on an exact sphere (closed, oriented, the right
-size), partial observation, the empty volume, and Gaussians -> mesh end to end.  The decision margins of the scenes are held on the CPU
-(tests/test_recon_geom_cpu.py)."""
+size), partial observation, the empty volume, and Gaussians -> mesh end to end.  Beside the shapes the kernels were written at: portrait
+images and one narrower than a tile, volumes whose launches end in a partial block (with guard elements behind every output), views
+that are not square, cameras inside the volume, random volumes that take nearly every corner-sign configuration of a cell, and planes that
+leave through the volume's border or pass through voxels whose mean is exactly 0.  The decision margins of the scenes and what each volume
+covers are held on the CPU (tests/test_recon_geom_cpu.py)."""
+import ctypes as C
 import types
 
 import numpy as np
@@ -66,20 +70,24 @@ def test_depth_and_alpha_match_the_fp64_oracle(hip_ops, case):
 
 
 def test_depth_pass_writes_no_pixel_outside_a_ragged_image(hip_ops):
-    W, H = 56, 40
-    scene, cam = R.depth_case(("random", D.SCENE_SEEDS[0], W, H, 0))
-    g = model(scene)
-    _, st = RZ.forward_pass(hip_ops, g.xyz, g.scaling, g.rotation, g.opacity, g.features_dc, RZ.gs_camera(cam, [0, 0, 0]))
-    lib = G.load_library()
-    pad = 64 * 48 - W * H          # the tiles cover 64 x 48 pixels
-    bufs = [torch.full((W * H + pad,), -7.0, device=DEV) for _ in range(2)]
-    rc = lib.v3d_recon_depth_alpha(st["ranges"].data_ptr(), st["vals_s"].data_ptr(), st["means2d"].data_ptr(), st["conic_opacity"].data_ptr(),
-                                   st["depth"].data_ptr(), st["n_contrib"].data_ptr(), W, H, bufs[0].data_ptr(), bufs[1].data_ptr(),
-                                   torch.cuda.current_stream().cuda_stream)
-    assert rc == 0, lib.v3d_recon_last_error()
-    depth, alpha = G.depth_alpha(st, W, H)
-    for b, m in zip(bufs, (depth, alpha)):
-        assert torch.equal(b[:W * H].view(H, W), m) and bool((b[W * H:] == -7.0).all())
+    # landscape, portrait, and a single column of tiles; (tiles cover)
+    for case, cover in ((("random", D.SCENE_SEEDS[0], 56, 40, 0), (64, 48)), (("random", 1116, 40, 56, 1), (48, 64)), (("random", 1116, 8, 24, 1), (16, 32))):
+        W, H = case[2:4]
+        scene, cam = R.depth_case(case)
+        g = model(scene)
+        _, st = RZ.forward_pass(hip_ops, g.xyz, g.scaling, g.rotation, g.opacity, g.features_dc, RZ.gs_camera(cam, [0, 0, 0]))
+        lib = G.load_library()
+        pad = cover[0] * cover[1] - W * H
+        assert cover == (-(-W // 16) * 16, -(-H // 16) * 16) and pad > 0
+        bufs = [torch.full((W * H + pad,), -7.0, device=DEV) for _ in range(2)]
+        rc = lib.v3d_recon_depth_alpha(st["ranges"].data_ptr(), st["vals_s"].data_ptr(), st["means2d"].data_ptr(), st["conic_opacity"].data_ptr(),
+                                       st["depth"].data_ptr(), st["n_contrib"].data_ptr(), W, H, bufs[0].data_ptr(), bufs[1].data_ptr(),
+                                       torch.cuda.current_stream().cuda_stream)
+        assert rc == 0, lib.v3d_recon_last_error()
+        depth, alpha = G.depth_alpha(st, W, H)
+        assert float(alpha.max()) > 0.5, "an empty view"
+        for b, m in zip(bufs, (depth, alpha)):
+            assert torch.equal(b[:W * H].view(H, W), m) and bool((b[W * H:] == -7.0).all()), (W, H)
 
 
 def test_no_gaussians_give_the_background_and_empty_maps():
@@ -92,34 +100,71 @@ def test_no_gaussians_give_the_background_and_empty_maps():
 
 
 # ---- TSDF -----------------------------------------------------------------------------------------------------------------------------
-def test_tsdf_matches_the_restatement():
-    case = R.sphere_tsdf_case()
+def integrate_case(case):
+    vol = G.new_volume(case["N"], case["bound"], case["trunc"])
+    for cam, (d, a, img) in zip(case["cams"], case["maps"]):
+        G.integrate_view(vol, d.to(DEV), a.to(DEV), img.to(DEV), cam, case["alpha_min"])
+    return vol
+
+
+@pytest.mark.parametrize("name", list(R.TSDF_CASES))
+def test_tsdf_matches_the_restatement(name):
+    case = R.sphere_tsdf_case(**R.TSDF_CASES[name])
     ref, near = R.sphere_tsdf_restatement(case)
     assert float(near.double().mean()) <= R.MAX_EXCLUDED
-    N = case["N"]
-
-    def run():
-        vol = G.new_volume(N, case["bound"])
-        for cam, (d, a, img) in zip(case["cams"], case["maps"]):
-            G.integrate_view(vol, d.to(DEV), a.to(DEV), img.to(DEV), cam)
-        return vol
-
-    vol, again = run(), run()
+    vol, again = integrate_case(case), integrate_case(case)
     assert vol.trunc == pytest.approx(ref["trunc"])
     for k in ("tsdf_sum", "weight", "rgb_sum", "rgb_weight"):
         assert torch.equal(getattr(vol, k), getattr(again, k)), f"{k} differs between two runs"
     keep = ~near
     w = vol.weight.cpu().double().reshape(-1)
-    assert torch.equal(w[keep], ref["weight"][keep])
-    assert torch.equal(vol.rgb_weight.cpu().double().reshape(-1)[keep], ref["rgb_weight"][keep])
     mean = vol.tsdf_sum.cpu().double().reshape(-1) / w.clamp_min(1)
     err = float((mean - ref["tsdf_sum"] / ref["weight"].clamp_min(1))[keep].abs().max())
     rgb_err = float((vol.rgb_sum.cpu().double().reshape(3, -1) - ref["rgb_sum"])[:, keep].abs().max())
     print(f"mean TSDF {err:.3e}  rgb_sum {rgb_err:.3e}  excluded {float(near.double().mean()):.3%}  differing weights among the excluded: "
-          f"{int((w != ref['weight'])[near].sum())}")
-    record_parity("recon_geom_tsdf", {"mean_tsdf_max_abs": err, "rgb_sum_max_abs": rgb_err, "excluded_share": float(near.double().mean())})
+          f"{int((w != ref['weight'])[near].sum())}, among the others: {int((w != ref['weight'])[keep].sum())}")
+    record_parity("recon_geom_tsdf" if name == "default" else f"recon_geom_tsdf[{name}]",
+                  {"mean_tsdf_max_abs": err, "rgb_sum_max_abs": rgb_err, "excluded_share": float(near.double().mean())})
+    assert torch.equal(w[keep], ref["weight"][keep])
+    assert torch.equal(vol.rgb_weight.cpu().double().reshape(-1)[keep], ref["rgb_weight"][keep])
     assert err <= 1e-5
-    assert rgb_err <= 1e-5          # sums of at most 4 colours in 0 .. 1 that both sides read from the same float32 image
+    assert rgb_err <= 1e-5          # sums of at most 5 colours in 0 .. 1 that both sides read from the same float32 image
+
+
+def test_tsdf_pass_writes_nothing_outside_a_ragged_volume():
+    """26^3 voxels end 168 threads into the last block.  The accumulators are the leading parts of buffers one block longer; the voxel just
+    past the volume lies inside one of the views (tests/test_recon_geom_cpu.py), so a thread let through there would write."""
+    case = R.sphere_tsdf_case(**R.TSDF_CASES[R.TSDF_CANARY_CASE])
+    N = case["N"]
+    n3 = N ** 3
+    assert n3 % 256 == 168
+    lib = G.load_library()
+    bufs = [torch.full((k * n3 + 256,), -7.0, device=DEV) for k in (1, 1, 3, 1)]       # tsdf_sum, weight, rgb_sum, rgb_weight
+    for b in bufs:
+        b[:-256] = 0
+    for cam, (d, a, img) in zip(case["cams"], case["maps"]):
+        d, a, img = d.to(DEV), a.to(DEV), img.to(DEV)
+        gc = RZ.gs_camera(cam, [0.0, 0.0, 0.0])
+        rc = lib.v3d_recon_tsdf_integrate(d.data_ptr(), a.data_ptr(), img.data_ptr(), C.byref(gc), N, case["bound"], case["trunc"], case["alpha_min"],
+                                          *(b.data_ptr() for b in bufs), torch.cuda.current_stream().cuda_stream)
+        assert rc == 0, lib.v3d_recon_last_error()
+    vol = integrate_case(case)
+    assert float(vol.weight.max()) == len(case["cams"]) and float(vol.rgb_weight.max()) > 0
+    for b, m in zip(bufs, (vol.tsdf_sum, vol.weight, vol.rgb_sum, vol.rgb_weight)):
+        assert torch.equal(b[:-256], m.reshape(-1)), "the leading part is not what integrate_view accumulates"
+        assert bool((b[-256:] == -7.0).all()), "a guard element behind the volume was written"
+
+
+def test_integrate_view_refuses_transposed_maps():
+    cam = D.cams_for(40, 24)[0]
+    vol = G.new_volume(8, 1.0)
+    t = lambda *shape: torch.zeros(*shape, device=DEV)  # noqa: E731
+    with pytest.raises(ValueError, match="do not match the 40 x 24 camera"):
+        G.integrate_view(vol, t(40, 24), t(40, 24), t(3, 40, 24), cam)
+    with pytest.raises(ValueError, match="do not match the 40 x 24 camera"):
+        G.integrate_view(vol, t(24, 40), t(24, 40), t(3, 40, 24), cam)
+    G.integrate_view(vol, t(24, 40), t(24, 40), t(3, 24, 40), cam)
+    assert not vol.rgb_weight.any()
 
 
 # ---- surface nets ---------------------------------------------------------------------------------------------------------------------
@@ -196,6 +241,79 @@ def test_empty_volume_gives_empty_arrays():
     assert verts.shape == (0, 3) and faces.shape == (0, 3) and colors.shape == (0, 3)
 
 
+@pytest.mark.parametrize("name", list(R.MESH_VOLUMES))
+def test_mesh_of_a_random_or_plane_volume_is_the_restatements(name):
+    """Every decision of the extraction is the sign of a numerator or a weight against 0, so the kernels and the fp64 restatement of the same
+    float32 values must agree on every cell, edge, index and winding; positions and colours are a few ulp of 1 apart."""
+    ref = R.MESH_VOLUMES[name]()
+    verts, faces, colors = (t.cpu() for t in G.extract_mesh(device_volume(ref)))
+    rv, rf, rc, _, _ = R.extract(R.promoted(ref))
+    assert verts.dtype == torch.float32 and faces.dtype == torch.int32 and colors.dtype == torch.float32
+    assert verts.shape == rv.shape and colors.shape == rc.shape and faces.shape == rf.shape and faces.shape[1] == 3
+    assert torch.equal(faces.long(), rf)
+    vert_err, col_err = float((verts.double() - rv).abs().max()), float((colors.double() - rc).abs().max())
+    grey = (rc == 0.5).all(1)          # a random volume's vertices with no coloured corner (a plane's colours are means that may land on 0.5)
+    print(f"{verts.shape[0]} vertices ({int(grey.sum())} grey), {faces.shape[0]} triangles; vertices {vert_err:.3e}  colours {col_err:.3e}")
+    record_parity(f"recon_geom_mesh[{name}]", {"vertices": int(verts.shape[0]), "triangles": int(faces.shape[0]), "grey_vertices": int(grey.sum()),
+                                               "vertex_max_abs": vert_err, "colour_max_abs": col_err})
+    assert vert_err <= 1e-6
+    assert col_err <= 1e-6
+    assert not name.startswith("random") or bool((colors[grey] == 0.5).all())
+    again = G.extract_mesh(device_volume(ref))
+    assert torch.equal(again[0].cpu(), verts) and torch.equal(again[1].cpu(), faces) and torch.equal(again[2].cpu(), colors)
+
+
+def test_one_cell_gives_a_vertex_and_no_faces():
+    verts, faces, colors = G.extract_mesh(device_volume(R.MESH_VOLUMES["random2"]()))
+    assert verts.shape == (1, 3) and colors.shape == (1, 3) and faces.shape == (0, 3) and faces.dtype == torch.int32
+
+
+def test_extraction_writes_nothing_outside_its_outputs(hip_ops):
+    """random_volume(13, 2): 12^3 cells and 3 * 13^3 edges both end in a partial block.  The five entries in extract_mesh's order, every
+    output the leading part of a buffer 256 elements longer."""
+    ref = R.MESH_VOLUMES["random13"]()
+    vol = device_volume(ref)
+    N = vol.resolution
+    m3, e3 = (N - 1) ** 3, 3 * N ** 3
+    assert m3 % 256 and e3 % 256 and N ** 3 % 256
+    lib, st = G.load_library(), torch.cuda.current_stream().cuda_stream
+    ts, w, rs, rw = (t.data_ptr() for t in (vol.tsdf_sum, vol.weight, vol.rgb_sum, vol.rgb_weight))
+    guarded = lambda n, dtype: torch.full((n + 256,), -7, dtype=dtype, device=DEV)  # noqa: E731
+    cflags = guarded(m3, torch.int32)
+    assert lib.v3d_recon_cells_flag(ts, w, N, cflags.data_ptr(), st) == 0, lib.v3d_recon_last_error()
+    coffs = hip_ops.gs_scan(cflags[:m3])
+    nv = int(coffs[-1])
+    verts, colors = guarded(3 * nv, torch.float32), guarded(3 * nv, torch.float32)
+    assert lib.v3d_recon_cells_vertices(ts, w, rs, rw, N, vol.bound, cflags.data_ptr(), coffs.data_ptr(), verts.data_ptr(), colors.data_ptr(), st) == 0, \
+        lib.v3d_recon_last_error()
+    eflags = guarded(e3, torch.int32)
+    assert lib.v3d_recon_edges_flag(ts, w, N, cflags.data_ptr(), eflags.data_ptr(), st) == 0, lib.v3d_recon_last_error()
+    eoffs = hip_ops.gs_scan(eflags[:e3])
+    ne = int(eoffs[-1])
+    faces = guarded(6 * ne, torch.int32)
+    assert lib.v3d_recon_edges_faces(ts, w, N, coffs.data_ptr(), eflags.data_ptr(), eoffs.data_ptr(), faces.data_ptr(), st) == 0, lib.v3d_recon_last_error()
+    ev, ef, ec = G.extract_mesh(vol)
+    assert (nv, 2 * ne) == (ev.shape[0], ef.shape[0]) and nv > 1000 and ne > 1000
+    for buf, n, out in ((verts, 3 * nv, ev), (colors, 3 * nv, ec), (faces, 6 * ne, ef)):
+        assert torch.equal(buf[:n], out.reshape(-1)), "the leading part is not what extract_mesh returns"
+    _, _, _, rflags, _ = R.extract(R.promoted(ref))
+    assert torch.equal(cflags[:m3].cpu().bool(), rflags) and int(eflags[:e3].sum()) == ne and bool(((eflags[:e3] == 0) | (eflags[:e3] == 1)).all())
+    for buf in (cflags, eflags, verts, colors, faces):
+        assert bool((buf[-256:] == -7).all()), "a guard element behind an output was written"
+
+
+def test_extract_mesh_refuses_other_types_and_devices():
+    ref = R.MESH_VOLUMES["random3"]()
+    vol = device_volume(ref)
+    vol.tsdf_sum = vol.tsdf_sum.double()
+    with pytest.raises(RuntimeError, match=r"tsdf_sum: expected a float32 tensor in device memory, got torch.float64 on cuda:0"):
+        G.extract_mesh(vol)
+    vol = device_volume(ref)
+    vol.rgb_weight = vol.rgb_weight.cpu()
+    with pytest.raises(RuntimeError, match=r"rgb_weight: expected a float32 tensor in device memory, got torch.float32 on cpu"):
+        G.extract_mesh(vol)
+
+
 # ---- end to end -----------------------------------------------------------------------------------------------------------------------
 def test_gaussians_to_mesh_end_to_end(tmp_path):
     """fuse_tsdf + extract_mesh on the kernels against the same views through the fp64 restatement (fp64-oracle depth and alpha).
@@ -219,3 +337,27 @@ def test_gaussians_to_mesh_end_to_end(tmp_path):
     assert v.shape == tuple(verts.shape) and f.shape == tuple(faces.shape) and c.shape == tuple(colors.shape) and v.shape[0] > 1000
     assert 0.3 < float(np.linalg.norm(v, axis=1).mean()) < 0.6             # a shell about the sphere of radius 0.5
     assert cd <= 4 * R.E2E_CHAMFER_FP32
+
+
+def test_gaussians_to_mesh_end_to_end_on_wide_views_and_a_ragged_volume():
+    """The same scene on 72 x 40 views and 30^3 voxels (30^3 = 105 * 256 + 120), at the bar of test_gaussians_to_mesh_end_to_end:
+    Chamfer(kernels, fp64 restatement) <= 4 x Chamfer(float32 restatement, fp64 restatement) as measured on the CPU
+    (R.E2E_CHAMFER_FP32_RAGGED); measured again here on the device and recorded."""
+    g = model(R.shell_scene())
+    W, H, N = (R.E2E_RAGGED[k] for k in ("W", "H", "N"))
+    assert N ** 3 % 256 == 120 and W != H
+    vol = G.fuse_tsdf(g, R.e2e_cameras(W, H), resolution=N, bound=R.E2E_BOUND, bg=[1.0, 1.0, 1.0])
+    verts, faces, colors = G.extract_mesh(vol)
+    ref64 = R.e2e_restatement(torch.float64, device=DEV, **R.E2E_RAGGED)
+    ref32 = R.e2e_restatement(torch.float32, device=DEV, **R.E2E_RAGGED)
+    cd32 = R.chamfer(ref32[0], ref64[0])
+    cd = R.chamfer(verts.cpu(), ref64[0])
+    print(f"Chamfer: kernels vs fp64 {cd:.3e}; float32 restatement vs fp64 {cd32:.3e} (on the CPU: {R.E2E_CHAMFER_FP32_RAGGED:.3e}); "
+          f"vertices {verts.shape[0]} vs {ref64[0].shape[0]}, triangles {faces.shape[0]} vs {ref64[1].shape[0]}")
+    record_parity("recon_geom_end_to_end[72x40-n30]",
+                  {"chamfer_kernels_vs_fp64": cd, "chamfer_float32_restatement_vs_fp64": cd32,
+                   "chamfer_float32_restatement_vs_fp64_cpu": R.E2E_CHAMFER_FP32_RAGGED, "vertices": int(verts.shape[0]),
+                   "vertices_fp64": int(ref64[0].shape[0]), "triangles": int(faces.shape[0])})
+    assert verts.shape[0] > 1000 and colors.shape == verts.shape and 0 <= int(faces.min()) and int(faces.max()) < verts.shape[0]
+    assert 0.3 < float(verts.norm(dim=1).mean()) < 0.6                       # a shell about the sphere of radius 0.5
+    assert cd <= 4 * R.E2E_CHAMFER_FP32_RAGGED

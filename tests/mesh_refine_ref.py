@@ -170,8 +170,8 @@ def view_schedule(num_opt_views, iterations, seed):
 
 
 @torch.no_grad()
-def frozen_view(pix_q, zv, faces, face_id, depth, V, dtype=torch.float64):
-    pv, pw = pixel_weights(pix_q, zv, faces, face_id, dtype=dtype)
+def frozen_view(pix_q, zv, faces, face_id, depth, V, dtype=torch.float64, bits=8):
+    pv, pw = pixel_weights(pix_q, zv, faces, face_id, bits=bits, dtype=dtype)
     return dict(pix_vert=pv, pix_w=pw, depth=depth.to(dtype), lists=vertex_lists(pv, V))
 
 

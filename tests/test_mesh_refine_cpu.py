@@ -169,14 +169,15 @@ def test_host_api_refuses_what_does_not_fit_and_shades_the_empty_mesh():
 
 # ---- the restatement's own honesty ----------------------------------------------------------------------------------------------------
 def _frozen(case, dtype=torch.float64):
-    kind, seed, W, H, _, cull = case
+    kind, seed, W, H, _, cull = case[:6]
+    bits = M.case_bits(case)
     v, f, c = M.mesh_scene(kind, seed)
-    pr = M.project(v, M.case_camera(case), 8, torch.float32)
-    r = M.rasterize(pr["pix_q"], pr["zv"], f, c, W, H, RF.BG, cull=cull)
-    return v, f, c, pr, r, RF.frozen_view(pr["pix_q"], pr["zv"], f, r["face_id"], r["depth"], v.shape[0], dtype)
+    pr = M.project(v, M.case_camera(case), bits, torch.float32)
+    r = M.rasterize(pr["pix_q"], pr["zv"], f, c, W, H, RF.BG, bits=bits, cull=cull)
+    return v, f, c, pr, r, RF.frozen_view(pr["pix_q"], pr["zv"], f, r["face_id"], r["depth"], v.shape[0], dtype, bits)
 
 
-@pytest.mark.parametrize("case", (M.RASTER_CASES[0], M.RASTER_CASES[9]), ids=M.case_id)
+@pytest.mark.parametrize("case", (M.RASTER_CASES[0], M.RASTER_CASES[9]) + M.REFINE_EDGE_CASES, ids=M.any_case_id)
 def test_restatement_shades_what_the_rasterizer_restatement_shades_and_its_transpose_is_autograd(case):
     v, f, c, pr, r, fz = _frozen(case)
     V = v.shape[0]

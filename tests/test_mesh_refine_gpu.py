@@ -1,8 +1,9 @@
 """The gfx950 vertex-colour refinement (csrc_recon/meshshade.hip, v3d_amd/recon/mesh_refine.py, scripts/pub/refine_mesh.py) against the torch
 restatement (tests/mesh_refine_ref.py): per-pixel vertices and weights, the shade, its transpose on real views, on synthetic lists and on a
 full-image quad, Adam on logits against torch.optim.Adam, the whole refinement on the project's own extracted sphere, the entry point, and
-the empty cases.  The restatement is fed the KERNEL'S OWN snapped positions, view z, face_id and depth, as tests/test_mesh_render_gpu.py
-does.
+the empty cases.  The weights, the shade and the transpose also run at 0, 4 and 7 sub-pixel bits on odd images and on one below a tile
+(mesh_render_ref.REFINE_EDGE_CASES).  The restatement is fed the KERNEL'S OWN snapped positions, view z, face_id and depth, as
+tests/test_mesh_render_gpu.py does.
 
 The bar everywhere is that file's: the kernel may be off from the fp64 restatement by 4x what the restatement's own float32 run is off.
 For the transposes "off" is measured two ways (mesh_refine_ref.row_errors): relative L2 over all rows, and the largest relative L2 of a
@@ -37,16 +38,22 @@ BG = [0.25, 0.5, 1.0]
 
 @functools.lru_cache(maxsize=None)
 def frozen(case):
-    """The kernel's view of a raster case and both restatements of it, computed once and shared (nothing below writes into them)"""
-    kind, seed, W, H, _, cull = case
+    """The kernel's view of a raster case (of RASTER_CASES at 8 sub-pixel bits, or of EDGE_CASES at its own) and both restatements of it,
+    computed once and shared (nothing below writes into them)"""
+    kind, seed, W, H, _, cull = case[:6]
+    bits = M.case_bits(case)
     cam = M.case_camera(case)
     v, f, c = M.mesh_scene(kind, seed)
     gc = gs_camera(cam, BG)
-    zv, _, pix_q = MR.project_vertices(gc, v.to(DEV))
-    view = RFN.prepare_view(cam, v, f, BG, cull=cull)
+    zv, _, pix_q = MR.project_vertices(gc, v.to(DEV), bits)
+    view = RFN.prepare_view(cam, v, f, BG, cull=cull, subpixel_bits=bits)
     host = dict(zv=zv.cpu(), pix_q=pix_q.cpu(), face_id=view.face_id.cpu(), depth=view.depth.cpu())
-    fz = {dt: RF.frozen_view(host["pix_q"], host["zv"], f, host["face_id"], host["depth"], v.shape[0], dt) for dt in (torch.float64, torch.float32)}
+    fz = {dt: RF.frozen_view(host["pix_q"], host["zv"], f, host["face_id"], host["depth"], v.shape[0], dt, bits) for dt in (torch.float64, torch.float32)}
     return cam, v, f, c, view, host, fz
+
+
+# every case of 8 sub-pixel bits, and 0, 4 and 7 bits on odd images and on one below a tile (mesh_render_ref.REFINE_EDGE_CASES)
+REFINE_CASES = M.RASTER_CASES + M.REFINE_EDGE_CASES
 
 
 def lists_of(view):
@@ -60,10 +67,11 @@ def lists_of(view):
 
 
 # ---- 1. weights and shade ---------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("case", M.RASTER_CASES, ids=M.case_id)
+@pytest.mark.parametrize("case", REFINE_CASES, ids=M.any_case_id)
 def test_weights_and_shade_match_the_restatement(case):
     cam, v, f, c, view, host, fz = frozen(case)
-    _, _, W, H, _, cull = case
+    _, _, W, H, _, cull = case[:6]
+    bits = M.case_bits(case)
     fid = host["face_id"].long()
     hit = fid >= 0
     assert 0.1 < float(hit.double().mean()) < 0.6
@@ -79,10 +87,10 @@ def test_weights_and_shade_match_the_restatement(case):
     ref = RF.shade(fz[torch.float64]["pix_vert"], fz[torch.float64]["pix_w"], fz[torch.float64]["depth"], c, BG)
     ref32 = RF.shade(fz[torch.float32]["pix_vert"], fz[torch.float32]["pix_w"], fz[torch.float32]["depth"], c, BG, torch.float32)
     ierr, ierr32 = float((img.double() - ref).abs().max()), float((ref32.double() - ref).abs().max())
-    full = MR.render_mesh(cam, v, f, c, BG, cull=cull)
+    full = MR.render_mesh(cam, v, f, c, BG, cull=cull, subpixel_bits=bits)
     same = bool(torch.equal(full["render"].cpu(), img))
     print(f"pix_w {werr:.3e} (float32 restatement {werr32:.3e})  image {ierr:.3e} ({ierr32:.3e})  bit-equal to render_mesh: {same}")
-    record_parity(f"mesh_refine_shade[{M.case_id(case)}]", {"pix_w_max_abs": werr, "pix_w_float32_restatement": werr32, "image_max_abs": ierr,
+    record_parity(f"mesh_refine_shade[{M.any_case_id(case)}]", {"pix_w_max_abs": werr, "pix_w_float32_restatement": werr32, "image_max_abs": ierr,
                                                             "image_float32_restatement": ierr32, "bit_equal_to_render_mesh": same})
     assert torch.equal(full["face_id"].cpu(), host["face_id"]) and torch.equal(full["depth"].cpu(), host["depth"])      # the same forward
     assert torch.equal(img[:, ~hit], torch.tensor(BG).view(3, 1).expand(3, int((~hit).sum())))
@@ -90,10 +98,10 @@ def test_weights_and_shade_match_the_restatement(case):
 
 
 # ---- 2. the transpose on real views -----------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("case", M.RASTER_CASES, ids=M.case_id)
+@pytest.mark.parametrize("case", REFINE_CASES, ids=M.any_case_id)
 def test_transpose_matches_the_restatement_on_real_views(case):
     cam, v, f, c, view, host, fz = frozen(case)
-    _, _, W, H, _, _ = case
+    _, _, W, H, _, _ = case[:6]
     V = v.shape[0]
     g = torch.Generator().manual_seed(7)
     dL = torch.randn(3, H, W, generator=g)
@@ -124,7 +132,7 @@ def test_transpose_matches_the_restatement_on_real_views(case):
                                fz[torch.float32]["lists"])
     (rel, row), (rel32, row32) = RF.row_errors(out, ref), RF.row_errors(ref32, ref)
     print(f"dL_dcolors rel L2 {rel:.3e} (float32 restatement {rel32:.3e})  worst row {row:.3e} ({row32:.3e})  {int((length == 0).sum())} of {V} rows empty")
-    record_parity(f"mesh_refine_transpose[{M.case_id(case)}]", {"rel_l2": rel, "rel_l2_float32_restatement": rel32, "worst_row_rel": row,
+    record_parity(f"mesh_refine_transpose[{M.any_case_id(case)}]", {"rel_l2": rel, "rel_l2_float32_restatement": rel32, "worst_row_rel": row,
                                                                 "worst_row_rel_float32_restatement": row32, "longest_list": int(length.max())})
     assert 0 < int((length == 0).sum()) < V and not out[length == 0].any()
     assert rel <= 4 * rel32 and row <= 4 * row32

@@ -1,7 +1,9 @@
 """The mesh rasterizer of libv3d_recon.so (csrc_recon/meshrast.hip, v3d_amd/recon/mesh_render.py, scripts/pub/render_mesh.py) without a GPU:
 the header, the ctypes table and the exports agree, bad arguments are refused before any launch, the script's options parse, the torch
 restatement (tests/mesh_render_ref.py) is itself honest about the fill rule and about closed meshes, and the scenes of
-tests/test_mesh_render_gpu.py keep their decision margins."""
+tests/test_mesh_render_gpu.py keep their decision margins and are what their tests need: the first seed that keeps the margin at every
+sub-pixel depth and size, the list shapes of the early-exit and tie scenes, the int64 headroom at the coordinate limit, the last column
+and row of the largest images."""
 import ctypes as C
 import importlib.util
 import os
@@ -249,3 +251,180 @@ def test_undrawn_mesh_is_undrawn_in_the_restatement():
             drawn, area2, _, tiles = M.drawn_faces(pr["pix_q"], f, 64, 48, 8, cull)
             assert not drawn.any() and not tiles.any(), [n for n, d in zip(names, drawn.tolist()) if d]
         assert int(area2[2]) != 0 and int(area2[3]) == 0 and int(area2[4]) == 0
+
+
+# ---- sub-pixel depths and ragged images: the premises of the edge cases ---------------------------------------------------------------
+def _edge_restated(case, seed=None):
+    kind, s, W, H, view, cull, bits = case
+    v, f, c = M.mesh_scene(kind, s if seed is None else seed)
+    pr = M.project(v, D.cams_for(W, H)[view], bits, torch.float32)      # (the GPU test uses the kernel's own snap; it asserts the premise on that again)
+    return pr, f, c, M.rasterize(pr["pix_q"], pr["zv"], f, c, W, H, [1, 1, 1], bits=bits, cull=cull)
+
+
+def test_edge_cases_pair_every_bit_depth_with_the_sizes_that_matter():
+    assert len(M.EDGE_CASES) == len({M.edge_case_id(c) for c in M.EDGE_CASES}) >= 16
+    assert {c[6] for c in M.EDGE_CASES} == set(M.EDGE_BITS) == {0, 1, 4, 7} and {(c[2], c[3]) for c in M.EDGE_CASES} == set(M.EDGE_SIZES)
+    assert set(M.EDGE_SIZES) == {(37, 21), (17, 50), (13, 9), (1, 1)}
+    for bits in M.EDGE_BITS:
+        sizes = {(c[2], c[3]) for c in M.EDGE_CASES if c[6] == bits}
+        assert any(W % 2 == 1 or H % 2 == 1 for W, H in sizes if (W, H) != (1, 1)) and any(W < 16 or H < 16 for W, H in sizes)
+        assert {c[5] for c in M.EDGE_CASES if c[6] == bits} == {True, False}                 # culling on and off at every bit depth
+        assert any(not c[5] and c[2] > 1 for c in M.EDGE_CASES if c[6] == bits)              # a closed scene with culling off: the parity of n_hit
+    for size in M.EDGE_SIZES:
+        assert len({c[6] for c in M.EDGE_CASES if (c[2], c[3]) == size}) >= 2
+    assert {c[0] for c in M.EDGE_CASES} == {"sphere", "pair"}
+    assert set(M.REFINE_EDGE_CASES) <= set(M.EDGE_CASES) and {0, 4} <= {c[6] for c in M.REFINE_EDGE_CASES}
+    assert all((c[2] % 2 == 1 or c[3] % 2 == 1) for c in M.REFINE_EDGE_CASES)
+
+
+@pytest.mark.parametrize("case", M.EDGE_CASES, ids=M.edge_case_id)
+def test_edge_scenes_keep_their_depth_margin(case):
+    """test_scenes_keep_their_depth_margin at 0, 1, 4 and 7 sub-pixel bits on odd images, images below a tile and a single pixel.  The seed
+    of a case is the FIRST that keeps the margin on every pixel (every smaller one breaks it); the one case without such a seed up to
+    SEED_LIMIT leaves at most EXCLUDE_MAX of its covered pixels out of the comparison of face_id, depth and colour."""
+    kind, seed, W, H, _, cull, bits = case
+    name = M.edge_case_id(case)
+    pr, f, c, r64 = _edge_restated(case)
+    assert not pr["marked"].any()
+    r32 = M.rasterize(pr["pix_q"], pr["zv"], f, c, W, H, [1, 1, 1], bits=bits, cull=cull, dtype=torch.float32)
+    keep, left_out = M.compared_pixels(r64, case)
+    covered = int((r64["n_hit"] > 0).sum())
+    gap, err = float(r64["gap"][keep].min()), float((r32["depth"].double() - r64["depth"])[keep].abs().max())
+    print(f"smallest gap {gap:.3e}, float32 restatement z error {err:.3e}, {covered} of {W * H} pixels covered, {left_out} left out")
+    assert gap >= M.Z_GAP_MARGIN and err <= M.Z_FP32_ERR
+    assert torch.equal(r32["face_id"][keep], r64["face_id"][keep]) and torch.equal(r32["n_hit"], r64["n_hit"])
+    if name in M.EDGE_EXCLUDING:
+        assert 0 < left_out <= M.EXCLUDE_MAX * covered and M.EDGE_SEEDS_TRIED[name] == M.SEED_LIMIT
+        for s in range(1, M.SEED_LIMIT + 1):                                              # no seed keeps the margin everywhere
+            assert float(_edge_restated(case, s)[3]["gap"].min()) < M.Z_GAP_MARGIN, s
+    else:
+        assert left_out == 0 and M.EDGE_SEEDS_TRIED[name] == seed
+        for s in range(1, seed):                                                          # counted up from 1: the smaller seeds break it
+            assert float(_edge_restated(case, s)[3]["gap"].min()) < M.Z_GAP_MARGIN, s
+    if not cull:
+        assert not (r64["n_hit"] % 2 == 1).any()                                          # both scenes are closed, snapped or not
+    if (W, H) == (1, 1):
+        assert covered == int(M.EDGE_SINGLE_PIXEL_COVERED[bits])
+    else:
+        assert 0.03 < covered / (W * H) < 0.6 and covered >= 20
+        dropped = int(((M.drawn_faces(pr["pix_q"], f, W, H, bits, False)[1] == 0)).sum())
+        print(f"{dropped} of {f.shape[0]} faces have no area after the snap")
+        if bits <= 1:
+            assert dropped >= 5                                                             # the snap flattens faces: the a2 == 0 drop is at work
+        if case in M.REFINE_EDGE_CASES:
+            assert 0.1 < covered / (W * H) < 0.6                                            # what the refinement's tests ask of a view
+
+
+# ---- the early exit where it must not fire; a tie across batches ----------------------------------------------------------------------
+def _synthetic(builder):
+    """The scene of the first seed counted up from 1 whose pixels all keep Z_GAP_MARGIN (TIE_PIXEL apart) in fp64 and decide alike in float32"""
+    for seed in range(1, M.SEED_LIMIT + 1):
+        q, zv, faces, colors = builder(seed=seed)
+        r64 = M.rasterize(q, zv, faces, colors, 56, 40, [0, 0, 0], cull=False)
+        r32 = M.rasterize(q, zv, faces, colors, 56, 40, [0, 0, 0], cull=False, dtype=torch.float32)
+        gap = r64["gap"].clone()
+        if builder is M.tie_across_batches:
+            gap[M.TIE_PIXEL[1], M.TIE_PIXEL[0]] = float("inf")
+        if float(gap.min()) >= M.Z_GAP_MARGIN and torch.equal(r32["face_id"], r64["face_id"]):
+            return seed, q, zv, faces, colors, r64, r32
+    raise AssertionError("no seed keeps the margin")
+
+
+def test_steep_cover_keeps_the_early_exit_from_firing():
+    seed, q, zv, faces, colors, r64, r32 = _synthetic(M.steep_cover)
+    assert seed == M.SYNTH_SEEDS["steep_cover"] == M.SYNTH_SEEDS_TRIED["steep_cover"]
+    F = faces.shape[0]
+    assert F == 1 + M.STEEP_FILLERS + M.STEEP_LAYERS < 1000 and bool(r64["drawn"].all())
+    zmin = zv[faces].min(1).values
+    first_layer = 1 + M.STEEP_FILLERS
+    assert float(zmin[0]) == 1.0 and bool((zmin[1:first_layer] > 1.0).all()) and bool((zmin[1:first_layer] < 2.0).all())
+    assert zmin[first_layer:].tolist() == pytest.approx([2.0 + 0.1 * k for k in range(M.STEEP_LAYERS)])
+    assert bool((r64["tiles"][1:first_layer] == 1).all())                         # every filler lies in one tile
+    idx, zsorted = M.tile_list(q, zv, faces, 56, 40)
+    assert idx.numel() == F > 2 * 256 and int(idx[0]) == 0 and bool((zsorted[1:] >= zsorted[:-1]).all())
+    pos = int(torch.nonzero(idx == first_layer)[0])
+    assert pos == first_layer >= 2 * 256 and set(idx[:pos].tolist()) == set(range(first_layer))       # in the third batch, behind face 0 and every filler
+    for batches in (1, 2):                                                        # every pixel of the tile is covered when batch 2 and batch 3 begin
+        head = M.rasterize(q, zv, faces[idx[:256 * batches]], colors, 56, 40, [0, 0, 0], cull=False)
+        assert bool((head["n_hit"][:16, :16] > 0).all())
+        assert int((head["depth"][:16, :16] >= float(zsorted[256 * batches])).sum()) > 50            # .. and not all in front of the batch's first zmin
+    tile = r64["face_id"][:16, :16]
+    only0 = M.rasterize(q, zv, faces[:1], colors, 56, 40, [0, 0, 0], cull=False)["depth"][:16, :16]
+    won = tile == first_layer
+    assert int(won.sum()) > 50 and bool((only0[won] > 2.0).all()) and int((tile == 0).sum()) > 50 and int(((tile > 0) & (tile < first_layer)).sum()) > 50
+    assert bool((r64["n_hit"][:16, :16] >= 1 + M.STEEP_LAYERS).all())
+
+
+def test_tie_across_batches_is_a_tie_in_float32_and_straddles_a_batch():
+    seed, q, zv, faces, colors, r64, r32 = _synthetic(M.tie_across_batches)
+    assert seed == M.SYNTH_SEEDS["tie_across_batches"] == M.SYNTH_SEEDS_TRIED["tie_across_batches"]
+    x, y = M.TIE_PIXEL
+    F = faces.shape[0]
+    assert F == 2 + M.TIE_FILLERS < 1000 and bool(r64["drawn"].all())
+    for r in (r64, r32):
+        two = M.rasterize(q, zv, faces[:2], colors, 56, 40, [0, 0, 0], cull=False, dtype=r["depth"].dtype)
+        assert int(two["n_hit"][y, x]) == 2 and float(two["gap"][y, x]) == 0.0 and float(two["depth"][y, x]) == 2.0       # both cover it, bit-equal
+        each = [M.rasterize(q, zv, faces[k:k + 1], colors, 56, 40, [0, 0, 0], cull=False, dtype=r["depth"].dtype) for k in (0, 1)]
+        assert float(each[0]["depth"][y, x]) == float(each[1]["depth"][y, x]) == 2.0
+        assert int(r["n_hit"][y, x]) == 2 and int(r["face_id"][y, x]) == 0 and float(r["depth"][y, x]) == 2.0             # no filler covers it
+        assert int((r["gap"] == 0).sum()) == 1                                                                            # the only tie
+    zmin = zv[faces].min(1).values
+    assert float(zmin[0]) == 2.0 and float(zmin[1]) == 1.5 and bool((zmin[2:] > 1.5).all()) and bool((zmin[2:] < 2.0).all())
+    idx, zsorted = M.tile_list(q, zv, faces, 56, 40)
+    p0, p1 = int(torch.nonzero(idx == 0)[0]), int(torch.nonzero(idx == 1)[0])
+    assert p1 == 0 and p0 == 2 * 256 == F - 1 and p0 - p1 - 1 >= 256              # the lower index later, 511 fillers and two batch boundaries between
+    assert float(zsorted[p0 - p0 % 256]) == 2.0                                   # its batch's first zmin EQUALS the depth the pixel holds: < or <= decides
+    # when that batch begins every pixel of the tile holds a depth at or in front of 2.0: an exit on <= would leave face 1 on the pixel
+    head = M.rasterize(q, zv, faces[idx[:p0]], colors, 56, 40, [0, 0, 0], cull=False, dtype=torch.float32)
+    assert bool((head["n_hit"][:16, :16] > 0).all()) and float(head["depth"][:16, :16].max()) == 2.0 and int(head["face_id"][y, x]) == 0      # (row 0 of the subset: face 1)
+    assert int(idx[0]) == 1
+
+
+def test_limit_triangle_stays_inside_int64():
+    W, H = 56, 40
+    q, zv, faces, colors = M.limit_triangle()
+    assert int(q[:3].abs().max()) == M.Q_EXTREME == 2 ** 28 - 3 and float(q[:3].abs().max()) < M.Q_LIMIT
+    assert len(set(zv[:3].tolist())) == 3
+    top = M.edge_intermediates_max(q, faces, W, H, 8)
+    assert 2 ** 57 < top < 2 ** 62
+    # the restatement's int64 tensors agree with unbounded integers on a corner pixel
+    r64 = M.rasterize(q, zv, faces, colors, W, H, [0, 0, 0], cull=False)
+    r32 = M.rasterize(q, zv, faces, colors, W, H, [0, 0, 0], cull=False, dtype=torch.float32)
+    assert bool(r64["drawn"].all()) and r64["tiles"].tolist() == [12, 9]
+    assert bool((r64["n_hit"] >= 1).all()) and set(r64["n_hit"].reshape(-1).tolist()) == {1, 2}      # face 0 holds the whole image, face 1 part of it
+    assert 100 < int((r64["face_id"] == 1).sum()) < W * H // 2 and torch.equal(r32["face_id"], r64["face_id"])
+    assert float(r64["gap"].min()) >= M.Z_GAP_MARGIN
+    far = r64["depth"][r64["face_id"] == 0]
+    assert float(far.max()) - float(far.min()) > 1e-5                                                # unequal corner depths show, if only just
+    a, b, c = (tuple(int(x) for x in q[i]) for i in range(3))
+    exact = ((b[0] - a[0]) * (c[1] - a[1]) - (b[1] - a[1]) * (c[0] - a[0]))
+    assert int(M.drawn_faces(q, faces, W, H, 8, False)[1][0]) == exact and abs(exact) > 2 ** 57
+
+
+@pytest.mark.parametrize("cull", (True, False), ids=("cull", "nocull"))
+@pytest.mark.parametrize("size", M.LIMIT_SIZES, ids=lambda s: f"{s[0]}x{s[1]}")
+def test_image_limit_scenes_reach_the_last_column_and_row(size, cull):
+    W, H = size
+    assert max(W, H) == 4096
+    seed = M.LIMIT_SEEDS[size]
+    assert M.LIMIT_SEEDS_TRIED[size] == seed == 1
+    v, f, c = M.mesh_scene("pair", seed)
+    pr = M.project(v, D.cams_for(W, H)[M.LIMIT_VIEW], 8, torch.float32)
+    assert not pr["marked"].any()
+    q, zv, ff, cc = M.with_extra(pr["pix_q"], pr["zv"], f, c, M.limit_extra(W, H))
+    r64 = M.rasterize(q, zv, ff, cc, W, H, [0, 0, 0], cull=cull)
+    r32 = M.rasterize(q, zv, ff, cc, W, H, [0, 0, 0], cull=cull, dtype=torch.float32)
+    F = f.shape[0]
+    assert bool(r64["drawn"][F:].all()) and int(r64["drawn"][:F].sum()) >= 30                       # the hand-placed faces and a slice of the pair
+    last = r64["face_id"][:, -1] if W > H else r64["face_id"][-1, :]
+    assert bool((last == F).any())                                                                  # the last column / row is covered
+    ys, xs = torch.nonzero(r64["face_id"] == F + 2, as_tuple=True)
+    assert (xs if W > H else ys).div(16, rounding_mode="floor").unique().numel() >= 100             # the long face wins pixels in 100 tiles and more
+    assert int(r64["face_id"][0, 0]) == F + 1
+    pair_ids = r64["face_id"][(r64["face_id"] >= 0) & (r64["face_id"] < F)]
+    assert pair_ids.numel() >= (1000 if W > H else 30) and pair_ids.unique().numel() >= 20            # (upright, the pair is 8 pixels across)
+    assert int(r64["tiles"][F + 2]) == 256                                                          # the long face is in every tile's list
+    gap, err = float(r64["gap"].min()), float((r32["depth"].double() - r64["depth"]).abs().max())
+    print(f"smallest gap {gap:.3e}, float32 restatement z error {err:.3e}, {int((r64['n_hit'] > 0).sum())} pixels covered")
+    assert gap >= M.Z_GAP_MARGIN and torch.equal(r32["face_id"], r64["face_id"]) and torch.equal(r32["n_hit"], r64["n_hit"])
+    assert M.edge_intermediates_max(q, ff[r64["drawn"]], W, H, 8) < 2 ** 62

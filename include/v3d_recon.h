@@ -282,6 +282,67 @@ int v3d_recon_mesh_decim_cut(const uint64_t* sel_keys_sorted, const uint32_t* se
 int v3d_recon_mesh_decim_apply(const int32_t* faces_in, int32_t num_faces, int32_t num_verts, const int32_t* accept, const int32_t* targets,
                                int32_t* faces_out, int32_t* live, double* quadrics, int32_t* removed, v3d_stream_t stream);
 
+/* ---- Mesh texture (v3d_amd/csrc_recon/meshtex.hip; host side: v3d_amd/recon/mesh_texture.py) ------------------------------------------------
+ * A texture for the decimated mesh, fitted against images of known cameras by the method of "Mesh colour refinement" with texels in the
+ * place of vertices: every view is rasterized once and frozen, the image is a gather of four texels per pixel, the gradient its transpose.
+ *   once:            v3d_recon_tex_face_uvs (for the writer), v3d_recon_tex_bake_vertex_colors (the initial albedo)
+ *   per view, once:  v3d_recon_mesh_render -> v3d_recon_mesh_pixel_weights -> v3d_recon_tex_pixel_texels -> scan of the coverage ->
+ *                    v3d_recon_tex_texel_records -> sort of the records on max(1, bits(R R - 1)) key bits -> v3d_recon_mesh_vertex_ranges with
+ *                    num_verts = R R;  the host then gathers ent_pix [n] = value / 4 and ent_w [n] = pix_tw[value] from the sorted values
+ *   per iteration:   v3d_recon_tex_shade -> (loss on the host side) -> v3d_recon_tex_shade_bwd -> v3d_recon_mesh_color_adam with num_verts = R R
+ * No atomics; the sort is stable, so a texel's entries stay in ascending 4 pixel + j and its thread adds them in that order.
+ *
+ * THE ATLAS.  The texture is R x R texels, R <= 4096, stored [R R][3] float32.  Texel (x, y) has index y R + x and its centre at coordinate
+ * (x, y) (the pixel convention of the rasterizer above).  Every face owns a right triangle of texels, by integer arithmetic on its index:
+ *   g = ceil(sqrt(ceil(F / 2))) cells per row;  cell size S = floor(R / g), at least 4 (a smaller one is refused: "texture too small");
+ *   face f lives in cell c = f >> 1 at origin (x0, y0) = ((c % g) S, (c / g) S), in half f & 1;  with L = S - 3 the UV corners of its places
+ *   0, 1, 2 are
+ *     half 0:  (x0, y0)                  (x0 + L, y0)                  (x0, y0 + L)
+ *     half 1:  (x0 + S-1, y0 + S-1)      (x0 + S-1 - L, y0 + S-1)      (x0 + S-1, y0 + S-1 - L)
+ *   (both halves have the same orientation);  the cell's texel (i, j) is owned by half 0 when i + j <= S - 2, else by half 1;  a texel outside
+ *   the g S square, or whose face index is >= F, is unowned.
+ * A sample anywhere in a face's UV triangle puts all of its bilinear 2 x 2 weight on texels the face owns: nothing bleeds between faces and
+ * this sampler needs no dilation.  No corner rotation and no multi-face charts: about half of the atlas is gutter. */
+#define V3D_RECON_TEX_MAX_SIZE 4096
+#define V3D_RECON_TEX_MIN_CELL 4
+
+/* One thread per face: vt [F][3][2], the UV corners above in texels. */
+int v3d_recon_tex_face_uvs(int32_t num_faces, int32_t tex_size, float* vt, v3d_stream_t stream);
+
+/* One thread per texel.  owner [R R]: the face that owns the texel, -1 when unowned.  texture [R R][3]: with (i, j) the texel's place in its
+ * cell, mirrored to (S-1-i, S-1-j) in half 1, b1 = clamp(i / L, 0, 1), b2 = clamp(j / L, 0, 1 - b1), b0 = 1 - b1 - b2 and the colour
+ * b0 c[v0] + b1 c[v1] + b2 c[v2] from colors [V][3] and the face's vertices;  `fill` on unowned texels and on the texels of a face with an
+ * index outside 0 .. V-1 (nothing is read through such an index). */
+int v3d_recon_tex_bake_vertex_colors(const int32_t* faces, int32_t num_faces, const float* colors, int32_t num_verts, int32_t tex_size, float fill,
+                                     int32_t* owner, float* texture, v3d_stream_t stream);
+
+/* One thread per pixel, on the face_id map of v3d_recon_mesh_render and the pix_w of v3d_recon_mesh_pixel_weights of the same view.
+ * beta_k = w_k / (w_0 + w_1 + w_2) (perspective-correct, sums to 1 by construction, free of the clamped depth);  (u, v) = sum beta_k corner_k,
+ * evaluated as corner_0 + beta_1 (corner_1 - corner_0) + beta_2 (corner_2 - corner_0) relative to the cell's origin (du = beta_1 L clamped
+ * to 0 .. L and dv = beta_2 L clamped to 0 .. L - du, counted from the right-angle corner: fp32 steps of a coordinate below S, not below R,
+ * and a sum that rounding cannot carry past the hypotenuse), which keeps it inside the chart's bounding box [lo, hi];  i0 = min(floor(u), hi_x - 1), j0 likewise, fu = u - i0, fv = v - j0.  pix_tex [H][W][4]: the indices of texels
+ * (i0, j0), (i0+1, j0), (i0, j0+1), (i0+1, j0+1);  pix_tw [H][W][4]: (1-fu)(1-fv), fu (1-fv), (1-fu) fv, fu fv.  -1 and 0 where face_id < 0
+ * (or is not below F, or the weights do not have a positive sum).  Every index written is inside 0 .. R R - 1 or is -1. */
+int v3d_recon_tex_pixel_texels(const int32_t* face_id, const float* pix_w, int32_t num_faces, int32_t tex_size, int32_t width, int32_t height,
+                               int32_t* pix_tex, float* pix_tw, v3d_stream_t stream);
+
+/* One thread per pixel: image [3][H][W], image[ch][p] = tw_0 T[t_0][ch] + tw_1 T[t_1][ch] + tw_2 T[t_2][ch] + tw_3 T[t_3][ch] from texture
+ * [R R][3];  bg0 bg1 bg2 where pix_tex[p][0] < 0 (or an index is outside the texture: nothing is read through it). */
+int v3d_recon_tex_shade(const int32_t* pix_tex, const float* pix_tw, const float* texture, int32_t tex_size, int32_t width, int32_t height, float bg0,
+                        float bg1, float bg2, float* image, v3d_stream_t stream);
+
+/* One thread per pixel: four records per covered pixel at rows 4 offsets[pixel] .. + 3 (offsets: exclusive scan of pix_tex[pixel][0] >= 0,
+ * num_records = 4 x its total, positive), keys = texel index, vals = 4 pixel + j: in pixel order. */
+int v3d_recon_tex_texel_records(const int32_t* pix_tex, const int32_t* offsets, int32_t width, int32_t height, int32_t num_records, uint64_t* keys,
+                                uint32_t* vals, v3d_stream_t stream);
+
+/* The transpose of the shade: dL_dtex [num_texels][3] from dL_dimage [3][H][W], dL_dtex[t][ch] = sum over the entries e of texel t of
+ * ent_w[e] dL_dimage[ch][ent_pix[e]].  One thread per texel adds its list front to back in fp32.  Every row is written, 0 0 0 for an empty
+ * list.  The arguments of v3d_recon_mesh_shade_bwd, which gives the same sums in another order with a 64-lane wave per row: on the
+ * documented path most lists are empty and the rest a few entries long.  num_entries may be 0 (ent_pix, ent_w NULL). */
+int v3d_recon_tex_shade_bwd(const int32_t* ranges, const int32_t* ent_pix, const float* ent_w, int32_t num_entries, const float* dL_dimage,
+                            int32_t width, int32_t height, int32_t num_texels, float* dL_dtex, v3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

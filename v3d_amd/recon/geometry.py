@@ -69,6 +69,13 @@ SIGNATURES = {
     "v3d_recon_mesh_decim_accept": (c_i32, [c_vp, c_vp, c_i32, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "v3d_recon_mesh_decim_cut": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp]),
     "v3d_recon_mesh_decim_apply": (c_i32, [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    # mesh texture (csrc_recon/meshtex.hip, v3d_amd/recon/mesh_texture.py)
+    "v3d_recon_tex_face_uvs": (c_i32, [c_i32, c_i32, c_vp, c_vp]),
+    "v3d_recon_tex_bake_vertex_colors": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_i32, c_f32, c_vp, c_vp, c_vp]),
+    "v3d_recon_tex_pixel_texels": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    "v3d_recon_tex_shade": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_f32, c_f32, c_f32, c_vp, c_vp]),
+    "v3d_recon_tex_texel_records": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    "v3d_recon_tex_shade_bwd": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
 }
 
 _lib = None

@@ -343,6 +343,62 @@ int v3d_recon_tex_texel_records(const int32_t* pix_tex, const int32_t* offsets, 
 int v3d_recon_tex_shade_bwd(const int32_t* ranges, const int32_t* ent_pix, const float* ent_w, int32_t num_entries, const float* dL_dimage,
                             int32_t width, int32_t height, int32_t num_texels, float* dL_dtex, v3d_stream_t stream);
 
+/* ---- Mesh vertex fit (v3d_amd/csrc_recon/meshdeform.hip; host side: v3d_amd/recon/mesh_deform.py) -----------------------------------------
+ * Moves the mesh's vertices so that its silhouette matches alpha maps of known cameras.  Visibility changes with every step, so nothing is
+ * frozen: every iteration runs the forward of "Mesh rasterizer" and then
+ *   v3d_recon_mesh_aa_alpha -> (loss on the host side) -> v3d_recon_mesh_aa_count -> scan of the counts -> v3d_recon_mesh_aa_emit -> sort of
+ *   the records on max(1, bits(V - 1)) key bits -> v3d_recon_mesh_vertex_ranges -> v3d_recon_mesh_aa_reduce -> v3d_recon_mesh_project_bwd
+ * (the scan and the sort are v3d_gs_scan and v3d_gs_radix_sort_pairs of libv3d_hip.so, called by the host).  No atomics: the sort is stable,
+ * so a vertex's records stay in pixel-then-neighbour-then-corner order, and one wave sums them in an order that the list alone decides.
+ *
+ * THE PAIR RULE.  A pair is a covered pixel p (face_id >= 0, face f) and one of its four neighbours q (right, left, down, up, in that
+ * order) that lies inside the image and has face_id < 0.  With the corners of f in pix_f (float32, unsnapped) and the edge k running from
+ * corner k to corner k + 1,  E_k(x) = s cross(v - u, x - u),  s = -1 where the doubled area of the SNAPPED corners (pix_q, int64) is negative
+ * and +1 otherwise: the rasterizer's own integer decision.  Every product and every difference of E_k is rounded to float32 on its own.
+ * The candidates are the edges with E_k(q) < 0;  for a candidate Ep = max(E_k(p), 0) and t_k = Ep / (Ep - E_k(q));  the pair's t is the
+ * smallest t_k, the lower k on equal t_k;  a pair without a candidate contributes nothing.  The pair adds t - 0.5 to its receiver: p when
+ * t < 0.5, else q.  A pixel's antialiased alpha is its coverage (1 or 0) plus what it receives, added in float32 in the order of the
+ * pixel's own neighbours, clamped to 0 .. 1.  Pairs between two covered pixels are not touched.  A face with an index outside 0 .. V-1 or
+ * a marked corner forms no pair. */
+
+/* One thread per pixel, a gather over its four neighbours.  face_id [H][W], faces [F][3], pix_f [V][2], pix_q [V][2]: the forward of the same
+ * view (cull = 1).  alpha_aa [H][W]: the clamped sum;  alpha_raw [H][W]: the sum before the clamp (the backward's clamp test). */
+int v3d_recon_mesh_aa_alpha(const int32_t* face_id, const int32_t* faces, int32_t num_faces, const float* pix_f, const int32_t* pix_q,
+                            int32_t num_verts, int32_t width, int32_t height, float* alpha_aa, float* alpha_raw, v3d_stream_t stream);
+
+/* One thread per pixel.  counts [H][W]: 2 x the number of the pixel's pairs that have a candidate (0 on a background pixel): the records it
+ * will emit.  pair_info [H][W][4] or NULL, for inspection: per neighbour -1 where there is no pair, -2 for a pair without a candidate, else
+ * the chosen edge k, + 4 when the receiver is the neighbour. */
+int v3d_recon_mesh_aa_count(const int32_t* face_id, const int32_t* faces, int32_t num_faces, const float* pix_f, const int32_t* pix_q,
+                            int32_t num_verts, int32_t width, int32_t height, int32_t* counts, int32_t* pair_info, v3d_stream_t stream);
+
+/* One thread per pixel: the records of pixel p at rows offsets[p] .. (offsets: exclusive scan of counts, num_records its total, positive), in
+ * neighbour order, the chosen edge's corner k before corner k + 1:  keys = vertex, vals = the record's own row, payload [n][2] = the record's
+ * dL/dpix_f.  dL/dt is dL_dalpha at the receiver, 0 where alpha_raw there lies outside the open interval (0, 1) or E_k(p) < 0 was clamped;
+ * dt/dEp = -Eq / (Ep - Eq)^2, dt/dEq = Ep / (Ep - Eq)^2, dE(x)/du = s (v_y - x_y, x_x - v_x), dE(x)/dv = s (x_y - u_y, u_x - x_x).  Records
+ * of value 0 are written too.  alpha_raw: that of v3d_recon_mesh_aa_alpha on the same arguments. */
+int v3d_recon_mesh_aa_emit(const int32_t* face_id, const int32_t* faces, int32_t num_faces, const float* pix_f, const int32_t* pix_q, int32_t num_verts,
+                           int32_t width, int32_t height, const float* alpha_raw, const float* dL_dalpha, const int32_t* offsets, int32_t num_records,
+                           uint64_t* keys, uint32_t* vals, float* payload, v3d_stream_t stream);
+
+/* dL_dpix [V][2] = the sum over the records of every vertex (ranges [V][2] of v3d_recon_mesh_vertex_ranges on the sorted keys, vals_sorted
+ * the sorted values) of payload[vals_sorted[e]].  One 64-lane wave per vertex: lane l adds entries start + l, start + l + 64, .. in list
+ * order, the lanes then meet in the xor butterfly of v3d_recon_mesh_shade_bwd.  Every row is written, 0 0 for an empty list.  num_records may
+ * be 0 (vals_sorted, payload NULL). */
+int v3d_recon_mesh_aa_reduce(const int32_t* ranges, const uint32_t* vals_sorted, const float* payload, int32_t num_records, int32_t num_verts,
+                             float* dL_dpix, v3d_stream_t stream);
+
+/* One thread per vertex: dL_dverts [V][3] from dL_dpix [V][2] through the statements of v3d_recon_mesh_project, the 1 / (hw + 1e-7) included.
+ * A marked vertex (pix_q INT32_MIN) gets 0 0 0. */
+int v3d_recon_mesh_project_bwd(const float* verts, int32_t num_verts, const v3d_gs_camera* cam, const int32_t* pix_q, const float* dL_dpix,
+                               float* dL_dverts, v3d_stream_t stream);
+
+/* One thread per vertex over the corner lists of "Mesh topology": grad [V][3] = scale x the sum over the vertex's list, in list order, of
+ * 2 d_i - d_j - d_k with d_j, d_k the offsets of the face's two other corners: the gradient of sum over faces and their 3 edges of
+ * |d_a - d_b|^2 when scale = 2 x the energy's own factor.  offsets [V][3].  0 0 0 for a vertex without faces. */
+int v3d_recon_mesh_smooth_grad(const float* offsets, int32_t num_verts, const int32_t* faces, int32_t num_faces, const int32_t* ranges,
+                               const int32_t* corners, float scale, float* grad, v3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -76,6 +76,13 @@ SIGNATURES = {
     "v3d_recon_tex_shade": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_f32, c_f32, c_f32, c_vp, c_vp]),
     "v3d_recon_tex_texel_records": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "v3d_recon_tex_shade_bwd": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
+    # mesh vertex fit (csrc_recon/meshdeform.hip, v3d_amd/recon/mesh_deform.py)
+    "v3d_recon_mesh_aa_alpha": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    "v3d_recon_mesh_aa_count": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    "v3d_recon_mesh_aa_emit": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    "v3d_recon_mesh_aa_reduce": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp]),
+    "v3d_recon_mesh_project_bwd": (c_i32, [c_vp, c_i32, _CAM, c_vp, c_vp, c_vp, c_vp]),
+    "v3d_recon_mesh_smooth_grad": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_f32, c_vp, c_vp]),
 }
 
 _lib = None

@@ -399,6 +399,64 @@ int v3d_recon_mesh_project_bwd(const float* verts, int32_t num_verts, const v3d_
 int v3d_recon_mesh_smooth_grad(const float* offsets, int32_t num_verts, const int32_t* faces, int32_t num_faces, const int32_t* ranges,
                                const int32_t* corners, float scale, float* grad, v3d_stream_t stream);
 
+/* ---- Mesh BVH and normal bake (v3d_amd/csrc_recon/meshbvh.hip; host side: v3d_amd/recon/mesh_bake.py) --------------------------------------
+ * "What does this ray hit" of one mesh, and with it a normal map of a high-poly mesh baked onto the atlas ("Mesh texture") of a low-poly one.
+ *   build:  v3d_recon_bvh_face_keys -> sort of the keys on 30 bits (v3d_gs_radix_sort_pairs, stable: equal codes stay in face order) ->
+ *           v3d_recon_bvh_build_nodes -> v3d_recon_bvh_fit_round until a round changes nothing
+ *   query:  v3d_recon_bvh_closest_hit;  v3d_recon_tex_bake_normals
+ * A linear BVH after Karras 2012.  No atomics.
+ *
+ * THE NODES.  F faces give 2 F - 1 nodes (2 F - 1 fits int32: F <= 2^30).  Internal nodes are 0 .. F-2, the root is node 0; leaf k (the k-th
+ * face in sorted order, face order[k]) is node F - 1 + k; with F = 1 there is no internal node and the lone leaf is the root.
+ * left [F-1], right [F-1]: the children of every internal node;  parent [2F-1]: -1 for the root;  lo [2F-1][3], hi [2F-1][3]: the node's
+ * axis-aligned box, for a leaf its face's, for an internal node the union of its leaves' (exact: min and max only).  A face with an index
+ * outside 0 .. V-1 has the empty box lo = +inf, hi = -inf, which adds nothing to a union, and is never hit.  The tree's height is at most
+ * 30 + bits(F - 1): 30 levels of code prefix, then the tie-break below. */
+#define V3D_RECON_BVH_STACK 64
+
+/* One thread per face.  face_lo, face_hi [F][3]: the face's box.  keys [F]: the 30-bit Morton code (x in the highest of every three bits) of
+ * the box centre 0.5 (lo + hi), every axis quantised to min(floor((c - lo_a) 1024 / (hi_a - lo_a)), 1023), 0 when that is not positive (a NaN
+ * centre included) or the mesh has no extent on the axis;  lo_*, hi_*: the bounding box of the mesh's vertices.  vals [F]: the face index. */
+int v3d_recon_bvh_face_keys(const float* verts, int32_t num_verts, const int32_t* faces, int32_t num_faces, float lo_x, float lo_y, float lo_z,
+                            float hi_x, float hi_y, float hi_z, uint64_t* keys, uint32_t* vals, float* face_lo, float* face_hi, v3d_stream_t stream);
+
+/* One thread per sorted position i: it places leaf i (lo, hi of node F - 1 + i from face_lo, face_hi of face order[i]) and, for i < F - 1,
+ * builds internal node i: its range of sorted positions by the common-prefix function delta(i, j) = clz(code_i ^ code_j) on the 32-bit words,
+ * 32 + clz(i ^ j) where the codes are equal, -1 for j outside 0 .. F-1, and its split;  it writes left[i], right[i] and its children's
+ * parent.  parent[0] = -1.  lo, hi of the internal nodes are left for v3d_recon_bvh_fit_round. */
+int v3d_recon_bvh_build_nodes(const uint64_t* keys_sorted, const uint32_t* order, const float* face_lo, const float* face_hi, int32_t num_faces,
+                              int32_t* left, int32_t* right, int32_t* parent, float* lo, float* hi, v3d_stream_t stream);
+
+/* One thread per internal node (F >= 2), between two buffers done_in, done_out [F-1] (zeros before the first round; a leaf is always done).
+ * A node that is done stays done.  A node whose two children are done in done_in writes the union of their boxes, is done in done_out and
+ * stores 1 to *changed;  any other node is not done in done_out.  A box written in round r is read from round r + 1 on: no launch reads what
+ * it writes.  The host swaps the buffers, runs the rounds in groups with a flag word each, and stops at the first round that stored nothing. */
+int v3d_recon_bvh_fit_round(const int32_t* left, const int32_t* right, int32_t num_faces, const int32_t* done_in, int32_t* done_out, float* lo,
+                            float* hi, int32_t* changed, v3d_stream_t stream);
+
+/* One thread per ray, 64 to a block, a stack of V3D_RECON_BVH_STACK nodes per ray in LDS.  rays_o, rays_d [N][3]: the direction is used as
+ * given, t is in units of it.  Triangle test (Moeller-Trumbore): e1 = v1 - v0, e2 = v2 - v0, p = d x e2, det = e1 . p (0: a miss), s = o - v0,
+ * u = (s . p) / det, q = s x e1, v = (d . q) / det, t = (e2 . q) / det;  a hit when u >= 0, v >= 0, u + v <= 1 and tmin <= t <= tmax.  cull,
+ * with Ng = e1 x e2: 0 every triangle, 1 only Ng . d < 0, 2 only Ng . d > 0.  The result is the smallest t and, on equal t, the smaller face
+ * index;  t [N], face [N], uv [N][2] = (u, v);  a miss gives +inf, -1, 0 0.  The box test is conservative (it never rejects a box the ray
+ * enters;  a zero direction component with the origin on a box plane, 0 x inf, puts no constraint on that axis), so only the triangle tests
+ * decide the result. */
+int v3d_recon_bvh_closest_hit(const float* rays_o, const float* rays_d, float tmin, float tmax, int32_t num_rays, int32_t cull, const int32_t* left,
+                              const int32_t* right, const uint32_t* order, const float* lo, const float* hi, const float* verts, int32_t num_verts,
+                              const int32_t* faces, int32_t num_faces, float* t, int32_t* face, float* uv, v3d_stream_t stream);
+
+/* One thread per texel of the low mesh's atlas (THE ATLAS above), 64 to a block.  owner [R R] and b0, b1, b2 are those of
+ * v3d_recon_tex_bake_vertex_colors.  P = b0 p0 + b1 p1 + b2 p2 from low_verts, n = b0 n0 + b1 n1 + b2 n2 from low_normals, divided by its
+ * length ((0, 0, 1) when the squared length is not above 1e-20).  Two casts against the high mesh (the tree, verts, faces above) by the
+ * rules of v3d_recon_bvh_closest_hit: from P along +n with cull = 2 and 0 <= t <= max_dist, from P along -n with cull = 1 and
+ * 0 < t <= max_dist;  the smaller t wins, +n on equal t.  normal_map [R R][3]: the high mesh's `normals` [V][3] at the hit,
+ * (1 - u - v) m0 + u m1 + v m2, divided by its length (the same rule);  n itself where neither cast hits;  (0, 0, 1) on unowned texels and
+ * on faces with an index outside the low vertices.  dist [R R]: +t or -t of the chosen hit, NaN without one.  hit_face [R R]: its face, or -1. */
+int v3d_recon_tex_bake_normals(const float* low_verts, int32_t low_num_verts, const int32_t* low_faces, int32_t low_num_faces, const float* low_normals,
+                               int32_t tex_size, float max_dist, const int32_t* left, const int32_t* right, const uint32_t* order, const float* lo,
+                               const float* hi, const float* verts, int32_t num_verts, const int32_t* faces, int32_t num_faces, const float* normals,
+                               int32_t* owner, float* normal_map, float* dist, int32_t* hit_face, v3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -83,6 +83,14 @@ SIGNATURES = {
     "v3d_recon_mesh_aa_reduce": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp]),
     "v3d_recon_mesh_project_bwd": (c_i32, [c_vp, c_i32, _CAM, c_vp, c_vp, c_vp, c_vp]),
     "v3d_recon_mesh_smooth_grad": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_f32, c_vp, c_vp]),
+    # mesh BVH and normal bake (csrc_recon/meshbvh.hip, v3d_amd/recon/mesh_bake.py)
+    "v3d_recon_bvh_face_keys": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_f32, c_f32, c_f32, c_f32, c_f32, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "v3d_recon_bvh_build_nodes": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "v3d_recon_bvh_fit_round": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "v3d_recon_bvh_closest_hit": (c_i32, [c_vp, c_vp, c_f32, c_f32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp,
+                                          c_vp, c_vp]),
+    "v3d_recon_tex_bake_normals": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp,
+                                           c_vp, c_vp, c_vp, c_vp, c_vp]),
 }
 
 _lib = None

@@ -457,6 +457,70 @@ int v3d_recon_tex_bake_normals(const float* low_verts, int32_t low_num_verts, co
                                const float* hi, const float* verts, int32_t num_verts, const int32_t* faces, int32_t num_faces, const float* normals,
                                int32_t* owner, float* normal_map, float* dist, int32_t* hit_face, v3d_stream_t stream);
 
+/* ---- Mesh queries (v3d_amd/csrc_recon/meshquery.hip; host side: v3d_amd/recon/mesh_query.py) ------------------------------------------------
+ * Three more questions to the tree of "Mesh BVH and normal bake" (THE NODES; the tree arguments come in the order of
+ * v3d_recon_bvh_closest_hit): the closest point of the mesh to a point, and with the midpoint samples of a mesh the distance between two
+ * meshes;  whether anything lies along a ray, and with a hemisphere of rays per texel an ambient-occlusion map on the atlas of "Mesh texture".
+ * No atomics.  Every walk keeps its stack of V3D_RECON_BVH_STACK nodes in LDS, is bounded by the node count and drops a push past the stack.
+ *
+ * THE CLOSEST POINT OF A TRIANGLE a, b, c to p (the region method; e1 = b - a, e2 = c - a, all in float):
+ *   d1 = e1 . (p - a), d2 = e2 . (p - a);            d1 <= 0 and d2 <= 0:              u, v = 0, 0                     (vertex a)
+ *   d3 = e1 . (p - b), d4 = e2 . (p - b);            else d3 >= 0 and d4 <= d3:        u, v = 1, 0                     (vertex b)
+ *   vc = d1 d4 - d3 d2;                              else vc <= 0, d1 >= 0, d3 <= 0:   u, v = d1 / (d1 - d3), 0        (edge a b)
+ *   d5 = e1 . (p - c), d6 = e2 . (p - c);            else d6 >= 0 and d5 <= d6:        u, v = 0, 1                     (vertex c)
+ *   vb = d5 d2 - d1 d6;                              else vb <= 0, d2 >= 0, d6 <= 0:   u, v = 0, d2 / (d2 - d6)        (edge a c)
+ *   va = d3 d6 - d5 d4, m = d4 - d3, n = d5 - d6;    else va <= 0, m >= 0, n >= 0:     w = m / (m + n); u, v = 1 - w, w  (edge b c)
+ *   else, with s = va + vb + vc:                                                       u, v = vb / s, vc / s           (inside)
+ * u and v weigh b and c as in the ray query.  The closest point is q = a + u e1 + v e2, but b itself where u == 1 and c itself where v == 1
+ * (a + (b - a) is rounded twice: a query at a vertex must be 0 away), and the squared distance is |p - q|^2 computed from q.  A dot product
+ * is (x x' + y y') + z z'. */
+
+/* One thread per point, 64 to a block.  points [N][3].  Every triangle tested gives (d2, u, v) by THE CLOSEST POINT OF A TRIANGLE.  Skipped:
+ * a face with an index outside 0 .. V-1;  a face with |e1 x e2|^2 == 0, taken as: in every component of e1 x e2 the two products, each
+ * rounded on its own, are equal;  a triangle whose d2 is not finite (a sliver whose sums underflow to 0 / 0, or an overflow).  The result is
+ * the smallest d2 and, on equal d2, the smaller face index, among the triangles with d2 <= max_dist^2 (closed;  max_dist may be +inf, NaN
+ * or a negative value is refused):  dist [N] = sqrtf(d2), face [N], uv [N][2] = (u, v).  A miss, also for a point with a coordinate that
+ * is not finite: +inf, -1, 0 0.  A node's bound is the squared distance from p to its box (c = min(max(p, lo), hi) per axis, |p - c|^2);
+ * of two children the one with the smaller bound is descended and the other pushed;  a node is skipped only when
+ * bound (1 - 2^-18) > best d2, strictly, so a box at exactly the best distance is still visited.  In exact arithmetic only the triangle
+ * tests decide the result.  In float they do up to the rounding of d2: q carries an error of a few ulps of the COORDINATES, so for a query
+ * much nearer to the surface than the coordinates are large the relative error of d2 can exceed the slack, and a leaf whose computed d2
+ * would have tied or won by less than that error can be skipped.  The answer is still a function of the arguments alone (two runs are
+ * bit-equal) and within that rounding of the smallest distance;  the smaller-face rule is exact among the triangles tested. */
+int v3d_recon_bvh_closest_point(const float* points, int32_t num_points, float max_dist, const int32_t* left, const int32_t* right,
+                                const uint32_t* order, const float* lo, const float* hi, const float* verts, int32_t num_verts,
+                                const int32_t* faces, int32_t num_faces, float* dist, int32_t* face, float* uv, v3d_stream_t stream);
+
+#define V3D_RECON_SAMPLES_MAX_SUBDIVIDE 16
+/* One thread per sample: the midpoint rule over n^2 congruent sub-triangles of every face, n = subdivide in 1 .. 16 (F n^2 must fit int32).
+ * Sample f n^2 + k:  for k < n (n + 1) / 2 an upright sub-triangle, k counting rows j = 0 .. n-1 of i = 0 .. n-1-j (i fastest), at
+ * b1, b2 = (i + t) / n, (j + t) / n with t = 1/3 rounded to float;  for the other k, k - n (n + 1) / 2 counts rows j = 0 .. n-2 of
+ * i = 0 .. n-2-j of inverted sub-triangles, the same with t = 2/3 rounded to float.  points [F n^2][3] = a + b1 e1 + b2 e2;
+ * weights [F n^2] = 0.5 sqrtf(|e1 x e2|^2) / n^2: the sub-triangle's area.  A face with an index outside 0 .. V-1: 0 0 0 and weight 0. */
+int v3d_recon_mesh_face_samples(const float* verts, int32_t num_verts, const int32_t* faces, int32_t num_faces, int32_t subdivide, float* points,
+                                float* weights, v3d_stream_t stream);
+
+#define V3D_RECON_OCCLUSION_MAX_SAMPLES 1024
+/* One wave (a block of 64 threads) per point;  lane l casts samples k = l, l + 64, ... < K, K = num_samples in 1 .. 1024;  the hits of every
+ * round of 64 are counted with a ballot and lane 0 writes hits [N].  points, normals [N][3].  A point with a coordinate that is not finite,
+ * or a normal whose squared length is not finite or not above 1e-20: hits = -1, nothing is cast.  n = normal / its length.
+ * DIRECTION k OF POINT i, in 32-bit unsigned arithmetic up to the conversion:  h = ((i + 1) 0x9E3779B9) ^ seed, then h ^= h >> 16,
+ * h *= 0x85EBCA6B, h ^= h >> 13, h *= 0xC2B2AE35, h ^= h >> 16;  frac = (float)(k 2654435769 + h) / 2^32;  u = (k + 0.5) / K,
+ * r = sqrtf(u), z = sqrtf(1 - u);  (sin, cos) of 2 pi frac by sincospif(2 frac);  s = copysignf(1, n.z), a = -1 / (s + n.z), b = n.x n.y a,
+ * t1 = (1 + s n.x^2 a, s b, -s n.x), t2 = (b, s + n.y^2 a, -n.y);  d = r cos t1 + r sin t2 + z n: cosine-weighted over the hemisphere of n,
+ * so the occlusion is hits / K.  The ray: origin p + bias n, 0 <= t <= radius (finite, > 0;  bias finite, >= 0), cull = 0, the triangle and
+ * box tests of v3d_recon_bvh_closest_hit with best = tmax;  the walk returns at the first triangle that is hit: a boolean of the set of
+ * triangles, which no order of the walk changes. */
+int v3d_recon_bvh_occlusion(const float* points, const float* normals, int32_t num_points, int32_t num_samples, float radius, float bias, uint32_t seed,
+                            const int32_t* left, const int32_t* right, const uint32_t* order, const float* lo, const float* hi, const float* verts,
+                            int32_t num_verts, const int32_t* faces, int32_t num_faces, int32_t* hits, v3d_stream_t stream);
+
+/* One thread per texel of the atlas (THE ATLAS above): owner [R R], P [R R][3] and n [R R][3] exactly as v3d_recon_tex_bake_normals forms
+ * them before it casts (b0, b1, b2 constant across the gutter;  n divided by its length, (0, 0, 1) when the squared length is not above
+ * 1e-20).  An unowned texel, and one whose face has an index outside the vertices: P = NaN NaN NaN, n = 0 0 1. */
+int v3d_recon_tex_texel_frames(const float* verts, int32_t num_verts, const int32_t* faces, int32_t num_faces, const float* normals, int32_t tex_size,
+                               int32_t* owner, float* positions, float* frame_normals, v3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -91,6 +91,12 @@ SIGNATURES = {
                                           c_vp, c_vp]),
     "v3d_recon_tex_bake_normals": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp,
                                            c_vp, c_vp, c_vp, c_vp, c_vp]),
+    # mesh queries (csrc_recon/meshquery.hip, v3d_amd/recon/mesh_query.py)
+    "v3d_recon_bvh_closest_point": (c_i32, [c_vp, c_i32, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    "v3d_recon_mesh_face_samples": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    "v3d_recon_bvh_occlusion": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_f32, c_f32, C.c_uint32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp,
+                                        c_vp]),
+    "v3d_recon_tex_texel_frames": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp]),
 }
 
 _lib = None

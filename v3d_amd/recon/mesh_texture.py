@@ -344,11 +344,12 @@ def _host(a, dtype):
     return (a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)).astype(dtype)
 
 
-def save_textured_obj(path: str, verts, faces, vt, texture, normal_map=None):
+def save_textured_obj(path: str, verts, faces, vt, texture, normal_map=None, ao_map=None):
     """Write <path> (.obj: v, vt, f a/ta b/tb c/tc, mtllib, usemtl), <stem>.mtl (map_Kd) and <stem>.png (8 bits).  vt [F, 3, 2] in texels
     (face_uvs); texture [R*R, 3] in 0 .. 1.  The file's vt is ((x + 0.5) / R, 1 - (y + 0.5) / R): v runs upwards in an OBJ.  With normal_map
     [R*R, 3] (object-space unit vectors on the same atlas: mesh_bake.bake_normal_map) also <stem>_normal.png, 0.5 n + 0.5 in 8 bits, and a
-    `norm` line in the MTL; without it the three files are what they were before the argument existed."""
+    `norm` line in the MTL; without it the three files are what they were before the argument existed.  With ao_map [R*R] (0 .. 1 on the same
+    atlas: mesh_query.bake_ambient_occlusion) also <stem>_ao.png, 8-bit greyscale, and a `map_Ka` line after the others; the same holds."""
     from PIL import Image
     v, f = _host(verts, np.float32).reshape(-1, 3), _host(faces, np.int64).reshape(-1, 3)
     uv, tex = _host(vt, np.float64).reshape(-1, 2), _host(texture, np.float32).reshape(-1, 3)
@@ -364,6 +365,11 @@ def save_textured_obj(path: str, verts, faces, vt, texture, normal_map=None):
         nm = _host(normal_map, np.float32).reshape(-1, 3)
         if nm.shape[0] != tex.shape[0]:
             raise ValueError(f"save_textured_obj: a normal map of {nm.shape[0]} texels beside a texture of {tex.shape[0]}")
+    ao = None
+    if ao_map is not None:
+        ao = _host(ao_map, np.float32).reshape(-1)
+        if ao.shape[0] != tex.shape[0]:
+            raise ValueError(f"save_textured_obj: an occlusion map of {ao.shape[0]} texels beside a texture of {tex.shape[0]}")
     stem = os.path.splitext(path)[0]
     name = os.path.basename(stem)
     Image.fromarray(np.floor(np.clip(tex, 0.0, 1.0) * 255.0 + 0.5).astype(np.uint8).reshape(R, R, 3)).save(stem + ".png")
@@ -371,6 +377,10 @@ def save_textured_obj(path: str, verts, faces, vt, texture, normal_map=None):
         fh.write(f"newmtl {name}\nKa 1 1 1\nKd 1 1 1\nKs 0 0 0\nillum 1\nmap_Kd {name}.png\n")
         if nm is not None:
             fh.write(f"norm {name}_normal.png\n")
+        if ao is not None:
+            fh.write(f"map_Ka {name}_ao.png\n")
+    if ao is not None:
+        Image.fromarray(np.floor(np.clip(ao, 0.0, 1.0) * 255.0 + 0.5).astype(np.uint8).reshape(R, R), mode="L").save(stem + "_ao.png")
     if nm is not None:
         Image.fromarray(np.floor(np.clip(0.5 * nm + 0.5, 0.0, 1.0) * 255.0 + 0.5).astype(np.uint8).reshape(R, R, 3)).save(stem + "_normal.png")
     lines = [f"mtllib {name}.mtl", f"usemtl {name}"]

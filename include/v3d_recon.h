@@ -521,6 +521,63 @@ int v3d_recon_bvh_occlusion(const float* points, const float* normals, int32_t n
 int v3d_recon_tex_texel_frames(const float* verts, int32_t num_verts, const int32_t* faces, int32_t num_faces, const float* normals, int32_t tex_size,
                                int32_t* owner, float* positions, float* frame_normals, v3d_stream_t stream);
 
+/* ---- Tangent space and GLB (v3d_amd/csrc_recon/meshtangent.hip; host side: v3d_amd/recon/mesh_gltf.py) ---------------------------------------
+ * What a glTF 2.0 file needs beside the atlas of "Mesh texture": per-corner NORMAL and TANGENT frames, the object-space normal map of "Mesh
+ * BVH and normal bake" re-expressed in those frames (glTF's normalTexture is in tangent space) and back, and a lit shade of one view from
+ * exactly that data.  No atomics, no LDS: a face, a texel and a pixel each belong to one thread.
+ *
+ * THE TANGENT FRAME.  Atlas texel row y is row y from the top of the written image, so the glTF TEXCOORD_0 of the atlas coordinate (x, y) is
+ * ((x + 0.5) / R, (y + 0.5) / R): no flip.  glTF's bitangent is w cross(N, T) and points along DECREASING glTF v.  A face's UV map is affine
+ * (THE ATLAS): with e1 = p1 - p0, e2 = p2 - p0 and s = +1 in half 0 (f & 1 == 0), -1 in half 1, dP/du = s e1 / L and dP/dv = s e2 / L.  Both
+ * halves have the same orientation: cross(dP/du, dP/dv) = e1 x e2 / L^2 whatever s is, so with N on the side of e1 x e2 and T along dP/du,
+ * cross(N, T) points along +dP/dv, which is INCREASING v, wherever the face looks in space.  Hence w = -1 on every corner of every face.
+ * (For normals on the OTHER side of the winding, N . (e1 x e2) < 0, the definition gives +1.  The project's vertex normals come from the
+ * winding;  w stays -1 for any normals given, and a reader that forms w cross(N, T) as glTF says still decodes exactly what was encoded.)
+ *   Per corner (f, k):  n = normals[faces[f][k]];  N = n / |n|, (0, 0, 1) where |n|^2 is not above 1e-20.  t' = s e1 - N (N . s e1);
+ *     T = t' / |t'|;  where |t'|^2 is not above 1e-20, T is the t1 of DIRECTION k OF POINT i built from N:  q = copysignf(1, N.z),
+ *     a = -1 / (q + N.z), b = N.x N.y a, T = (1 + q N.x^2 a, q b, -q N.x).  w = -1.
+ *   Per point of a face with barycentrics b:  vN = sum b_k N_k, vT = sum b_k T_k, neither normalised;  vB = w cross(vN, vT).  (What the
+ *     consumers of MikkTSpace tangents do per pixel.)
+ *   Decode a map value c:  n = c.x vT + c.y vB + c.z vN, divided by its length;  where |n|^2 is not above 1e-20, vN divided by its length;
+ *     where |vN|^2 is not above 1e-20 either, (0, 0, 1).
+ *   Encode an object-space vector m, the exact inverse:  det = vT . (vB x vN);  c = (m . (vB x vN), m . (vN x vT), m . (vT x vB)) / det,
+ *     divided by its length;  (0, 0, 1) where det is not finite, where |det| <= 1e-12, or where |c|^2 is not above 1e-20 (or is not finite).
+ * A dot product is (x x' + y y') + z z'. */
+#define V3D_RECON_LIT_MAX_LIGHTS 4
+
+/* One thread per face: corner_normals [3F][3] = N and corner_tangents [3F][4] = (T, w) of THE TANGENT FRAME, corner 3 f + k being place k of
+ * face f;  verts [V][3], faces [F][3], normals [V][3] (v3d_recon_mesh_vertex_normals, or any others).  A face with an index outside 0 .. V-1
+ * writes (0, 0, 1) and (1, 0, 0, -1) three times;  nothing is read through such an index. */
+int v3d_recon_tex_corner_frames(const float* verts, int32_t num_verts, const int32_t* faces, int32_t num_faces, const float* normals,
+                                float* corner_normals, float* corner_tangents, v3d_stream_t stream);
+
+/* One thread per texel of the atlas.  owner [R R] and b0, b1, b2 are those of v3d_recon_tex_bake_vertex_colors (constant across the
+ * gutter);  vN, vT, vB from the owner's three rows of corner_normals, corner_tangents (w is read from corner 0's tangent).  tangent_map
+ * [R R][3] = the encoding of object_map [R R][3] by THE TANGENT FRAME: float unit vectors, not yet 0.5 c + 0.5.  (0, 0, 1) on unowned
+ * texels and on the texels of a face with an index outside 0 .. V-1 (faces is read for that test alone). */
+int v3d_recon_tex_encode_tangent(const int32_t* faces, int32_t num_faces, int32_t num_verts, const float* corner_normals, const float* corner_tangents,
+                                 const float* object_map, int32_t tex_size, int32_t* owner, float* tangent_map, v3d_stream_t stream);
+
+/* The inverse, with the same arguments and the two maps exchanged: object_map [R R][3] = the decoding of tangent_map [R R][3];  (0, 0, 1)
+ * on the same texels.  With the frames of a mesh that has moved since the bake and the old tangent map, this is the new object-space map. */
+int v3d_recon_tex_decode_tangent(const int32_t* faces, int32_t num_faces, int32_t num_verts, const float* corner_normals, const float* corner_tangents,
+                                 const float* tangent_map, int32_t tex_size, int32_t* owner, float* object_map, v3d_stream_t stream);
+
+/* One thread per pixel, on face_id [H][W], pix_w [H][W][3], pix_tex, pix_tw [H][W][4] of one view (v3d_recon_mesh_render,
+ * v3d_recon_mesh_pixel_weights, v3d_recon_tex_pixel_texels).  A pixel is covered when 0 <= face_id < F, w_0 + w_1 + w_2 > 0 and its four
+ * texel indices lie inside 0 .. R R - 1.  beta_k = w_k / (w_0 + w_1 + w_2);  vN, vT, vB at beta from the face's corner frames;
+ * c = sum_j tw_j C[t_j] from tangent_map [R R][3] (float, as v3d_recon_tex_encode_tangent writes it), (0, 0, 1) when tangent_map is NULL;
+ * n = the decoding of c;  albedo = sum_j tw_j A[t_j] from albedo [R R][3];  ao = sum_j tw_j O[t_j] from ao_map [R R], 1 when ao_map is
+ * NULL.  image [3][H][W]:  image[ch] = albedo[ch] (ambient ao + sum_k I_k max(0, n . d_k)) over K = num_lights in 0 .. 4 directional lights,
+ * d_k = light_dirs[k] (world space, pointing TOWARDS the light, unit: the caller normalises), I_k = light_intensity[k];  not clamped;
+ * bg0 bg1 bg2 where the pixel is not covered.  normals [3][H][W]: n, 0 0 0 where the pixel is not covered.  light_dirs [K][3] and
+ * light_intensity [K] are HOST arrays, read before the call returns (NULL when K = 0). */
+int v3d_recon_tex_shade_lit(const int32_t* face_id, const float* pix_w, const int32_t* pix_tex, const float* pix_tw, int32_t num_faces,
+                            const float* corner_normals, const float* corner_tangents, const float* tangent_map, const float* albedo,
+                            const float* ao_map, int32_t tex_size, int32_t width, int32_t height, int32_t num_lights, const float* light_dirs,
+                            const float* light_intensity, float ambient, float bg0, float bg1, float bg2, float* image, float* normals,
+                            v3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

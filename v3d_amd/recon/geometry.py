@@ -97,6 +97,12 @@ SIGNATURES = {
     "v3d_recon_bvh_occlusion": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_f32, c_f32, C.c_uint32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp,
                                         c_vp]),
     "v3d_recon_tex_texel_frames": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    # tangent space and GLB (csrc_recon/meshtangent.hip, v3d_amd/recon/mesh_gltf.py)
+    "v3d_recon_tex_corner_frames": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    "v3d_recon_tex_encode_tangent": (c_i32, [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp]),
+    "v3d_recon_tex_decode_tangent": (c_i32, [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp]),
+    "v3d_recon_tex_shade_lit": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_f32, c_f32,
+                                        c_f32, c_f32, c_vp, c_vp, c_vp]),
 }
 
 _lib = None

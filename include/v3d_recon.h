@@ -521,6 +521,67 @@ int v3d_recon_bvh_occlusion(const float* points, const float* normals, int32_t n
 int v3d_recon_tex_texel_frames(const float* verts, int32_t num_verts, const int32_t* faces, int32_t num_faces, const float* normals, int32_t tex_size,
                                int32_t* owner, float* positions, float* frame_normals, v3d_stream_t stream);
 
+/* ---- Mesh solid (v3d_amd/csrc_recon/meshsolid.hip; host side: v3d_amd/recon/mesh_solid.py) --------------------------------------------------
+ * "Am I inside" of the tree of "Mesh BVH and normal bake" (THE NODES; the tree arguments come in the order of v3d_recon_bvh_closest_hit):
+ * the generalized winding number (Jacobson et al. 2013), summed hierarchically with one dipole per node (the first order of Barill et al.
+ * 2018), and with the closest point of "Mesh queries" a signed distance and a volume of v3d_recon_tsdf_integrate filled from a mesh, open or closed.
+ *   moments:  v3d_recon_bvh_moment_round until a round changes nothing, after the fit's boxes are final
+ *   query:    v3d_recon_bvh_winding;  v3d_recon_sdf_grid
+ * No atomics.  Every kernel is launched in blocks of one wave;  every walk keeps its stack of V3D_RECON_BVH_STACK nodes in LDS
+ * (stack[entry * 64 + lane]), is bounded by the node count and drops a push past the stack.
+ *
+ * THE WINDING NUMBER.  For a query q and a triangle v0 v1 v2, with a = v0 - q, b = v1 - q, c = v2 - q, all in float:
+ *   num = a . (b x c),   den = |a| |b| |c| + (a . b) |c| + (b . c) |a| + (c . a) |b|,   Omega = 2 atan2f(num, den),
+ *   Omega = 0 where num == 0 (a query in the triangle's plane: on the triangle, where the angle has no value, and beside it, where it is 0),
+ *   Omega = 0 for a face with an index outside 0 .. V-1.   w(q) = sum of Omega over the faces / (4 pi).
+ * A triangle wound so that e1 x e2 points outward gives +1 inside a closed mesh, 0 outside;  the same mesh wound inward gives -1 inside.
+ * A dot product is (x x' + y y') + z z';  |x| = sqrtf(x . x).
+ *
+ * THE MOMENTS.  mom [2F-1][8] float, a row per node of THE NODES: (nx, ny, nz, r2, cx, cy, cz, area).
+ *   Leaf of a face whose indices are vertices:  n = 0.5 e1 x e2 (e1 = v1 - v0, e2 = v2 - v0);  area = |n|;  c = ((v0 + v1) + v2) / 3.
+ *     A face without area as v3d_recon_bvh_closest_point takes it (in every component of e1 x e2 the two products are equal) has n = 0 and
+ *     area = 0 exactly, and keeps its c.
+ *   Leaf of a face with an index outside 0 .. V-1:  all zeros.
+ *   Internal node, from its children l, r:  n = n_l + n_r;  area = a_l + a_r;  c = (a_l c_l + a_r c_r) / area where area > 0, otherwise
+ *     the centre 0.5 (lo + hi) of the node's box, or 0 0 0 for the empty box.
+ *   Every node:  r2 = (mx + my) + mz with m_k = max((c_k - lo_k)^2, (hi_k - c_k)^2) on the node's own box: the squared distance from c to
+ *     the box's farthest corner, a bound on everything below the node;  r2 = 0 for the empty box (lo > hi on an axis).
+ *
+ * THE SUM.  The walk starts at the root, descends the left child and pushes the right (depth <= height <= V3D_RECON_BVH_STACK), so the
+ * order of the sum is a function of the tree alone.  With d = c - q and d2 = d . d:
+ *   a node with area == 0 adds nothing and is not descended;
+ *   a node, leaf or internal, is FAR when beta^2 > 0 and d2 > beta^2 r2 (beta^2 and the product in float);  it adds (n . d) / (d2 sqrtf(d2));
+ *   a leaf that is not far adds its Omega;   an internal node that is not far is opened.
+ * beta == 0 never approximates: the sum is THE WINDING NUMBER's own.  Every term is computed in float;  the running sum is a double,
+ * divided by 4 pi in double and rounded to float once.  A query with a coordinate that is not finite answers NaN without a walk. */
+
+/* One thread per node, 64 to a block, between two buffers done_in, done_out [2F-1] (zeros before the first round;  unlike the fit's they
+ * hold the leaves too).  A node that is done stays done.  A leaf that is not done writes its row of THE MOMENTS (so the first round writes
+ * the leaves), an internal node whose two children are done in done_in writes its row from theirs;  both are done in done_out and store 1
+ * to *changed;  any other node is not done in done_out.  A row written in round r is read from round r + 1 on: no launch reads a row it
+ * writes.  The host runs the rounds as it runs v3d_recon_bvh_fit_round, AFTER the boxes are final (lo, hi are read, never written).  F = 1:
+ * one round writes the lone leaf. */
+int v3d_recon_bvh_moment_round(const int32_t* left, const int32_t* right, const uint32_t* order, const float* lo, const float* hi, const float* verts,
+                               int32_t num_verts, const int32_t* faces, int32_t num_faces, const int32_t* done_in, int32_t* done_out, float* mom,
+                               int32_t* changed, v3d_stream_t stream);
+
+/* One thread per query, 64 to a block.  points [N][3];  w [N] by THE SUM with `beta` (finite, >= 0;  0: the exact sum) on mom [2F-1][8]. */
+int v3d_recon_bvh_winding(const float* points, int32_t num_points, float beta, const int32_t* left, const int32_t* right, const uint32_t* order,
+                          const float* lo, const float* hi, const float* verts, int32_t num_verts, const int32_t* faces, int32_t num_faces,
+                          const float* mom, float* w, v3d_stream_t stream);
+
+/* One thread per voxel of a volume of v3d_recon_tsdf_integrate (voxel (ix, iy, iz) at [iz][iy][ix], N in 2 .. V3D_RECON_MAX_N).  A block of 64 threads is a
+ * 4 x 4 x 4 brick: lane l is voxel (4 bx + (l & 3), 4 by + ((l >> 2) & 3), 4 bz + (l >> 4)) of block (bx, by, bz) in a grid of
+ * ceil(N / 4)^3;  lanes outside the volume idle.  The result does not depend on this mapping.  The voxel's centre on every axis is
+ * fmaf(i + 0.5, voxel, -bound) with voxel = 2 bound / N in float: the exact (i + 0.5) voxel - bound rounded to float once.  Per voxel:
+ * the closest point by v3d_recon_bvh_closest_point's rules with max_dist = trunc (closed), then w by THE SUM;  s = -1 where w >= 0.5, else
+ * +1 (a NaN w gives +1).  tsdf_sum = s min(dist / trunc, 1), or s on a miss;  weight = 1 always;  on a hit and with colors [V][3] given,
+ * rgb_sum [3][N][N][N] = (1 - u - v) c0 + u c1 + v c2 of the closest face's vertex colours and rgb_weight = 1;  on a miss, or with colors
+ * NULL (no colour is read), both are 0.  Negative is inside, as v3d_recon_cells_flag takes it.  bound and trunc finite and positive. */
+int v3d_recon_sdf_grid(const int32_t* left, const int32_t* right, const uint32_t* order, const float* lo, const float* hi, const float* verts,
+                       int32_t num_verts, const int32_t* faces, int32_t num_faces, const float* mom, const float* colors, int32_t resolution, float bound,
+                       float trunc, float beta, float* tsdf_sum, float* weight, float* rgb_sum, float* rgb_weight, v3d_stream_t stream);
+
 /* ---- Tangent space and GLB (v3d_amd/csrc_recon/meshtangent.hip; host side: v3d_amd/recon/mesh_gltf.py) ---------------------------------------
  * What a glTF 2.0 file needs beside the atlas of "Mesh texture": per-corner NORMAL and TANGENT frames, the object-space normal map of "Mesh
  * BVH and normal bake" re-expressed in those frames (glTF's normalTexture is in tangent space) and back, and a lit shade of one view from

@@ -97,6 +97,11 @@ SIGNATURES = {
     "v3d_recon_bvh_occlusion": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_f32, c_f32, C.c_uint32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp,
                                         c_vp]),
     "v3d_recon_tex_texel_frames": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    # mesh solid (csrc_recon/meshsolid.hip, v3d_amd/recon/mesh_solid.py)
+    "v3d_recon_bvh_moment_round": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "v3d_recon_bvh_winding": (c_i32, [c_vp, c_i32, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp]),
+    "v3d_recon_sdf_grid": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_i32, c_f32, c_f32, c_f32, c_vp, c_vp, c_vp, c_vp,
+                                   c_vp]),
     # tangent space and GLB (csrc_recon/meshtangent.hip, v3d_amd/recon/mesh_gltf.py)
     "v3d_recon_tex_corner_frames": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "v3d_recon_tex_encode_tangent": (c_i32, [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp]),

@@ -639,6 +639,87 @@ int v3d_recon_tex_shade_lit(const int32_t* face_id, const float* pix_w, const in
                             const float* light_intensity, float ambient, float bg0, float bg1, float bg2, float* image, float* normals,
                             v3d_stream_t stream);
 
+/* ---- Mesh remeshing (v3d_amd/csrc_recon/meshremesh.hip; host side: v3d_amd/recon/mesh_remesh.py) -------------------------------------------
+ * Isotropic remeshing towards a target edge length L (Botsch & Kobbelt 2004): split the edges longer than hi = 4/3 L, collapse those shorter
+ * than lo = 4/5 L, flip edges towards valence 6 (4 on an open edge), relax the vertices in their tangent planes, put them back on the input.
+ * THE STATE: verts [Vcap][3], colors [Vcap][3], faces [Fcap][3] and counts [2] = (V_live, F_live) on the device: rows 0 .. V_live-1 and
+ * 0 .. F_live-1 have been born.  Every entry is called with num_verts = Vcap and num_faces = Fcap.  A dead or unborn face holds Vcap in all
+ * three places (the rule of "Mesh decimation": absent for every entry); an unborn vertex has no face.  Only a split moves the counts.
+ *   per round:  the corner lists of "Mesh decimation" (with Vcap + 1 vertices) -> one of the three propose entries -> keys [V], targets [V] ->
+ *               v3d_recon_mesh_decim_min_round twice -> v3d_recon_mesh_decim_accept with max_error = +inf -> (split only: v3d_gs_scan of accept,
+ *               rank [V + 1]) -> the matching apply entry, which edits the faces IN PLACE
+ *   once per iteration:  v3d_recon_remesh_relax between two buffers;  v3d_recon_bvh_closest_point against the tree of the INPUT mesh, then
+ *               v3d_recon_remesh_project
+ *   at the end: v3d_recon_mesh_compact_faces
+ * THE KEY of a proposal by vertex v: fp32 bits of a finite priority >= 0 (smaller is sooner) << 32 | (v * 0x9E3779B1 mod 2^32); all ones for no
+ * proposal (targets[v] = -1).  The multiplier is odd, so keys stay distinct; the apply entries read accept[v] and never decode a key.
+ * Accepted vertices are at least 3 edges apart, so their one-rings share no vertex and no face; every apply thread reads and writes only
+ * faces of its own vertex's list and reads all of them before its first store.  One thread per vertex; no atomics; no local arrays;
+ * bit-reproducible.  Squared lengths are float, (dx dx + dy dy) + dz dz; hi^2 = (16/9) (L L) and lo^2 = (16/25) (L L) in float; normal tests
+ * are fp64; nothing is contracted.  The valence of a vertex is the number of its faces.  A vertex with more than max_valence faces (3 ..
+ * V3D_RECON_MESH_MAX_VALENCE) proposes nothing, and no list longer than that is ever walked to its end.
+ * THE EDGE (a, b) IS EDITABLE when exactly one entry of a's list has b as its next corner (the face (a, b, c), c its previous corner) and
+ * exactly one has b as its previous corner (the face (b, a, d), d its next corner), and a, b, c, d are four different vertices: an open
+ * edge, a non-manifold edge and an edge of a folded pair of faces are never edited. */
+
+/* Split.  a proposes, among its editable edges (a, b) with len^2 > hi^2, the longest; the smaller b among equals.  Priority L L / len^2;
+ * targets[a] = b. */
+int v3d_recon_remesh_split_propose(const float* verts, int32_t num_verts, const int32_t* faces, int32_t num_faces, const int32_t* ranges,
+                                   const int32_t* corners, float target_edge, int32_t max_valence, uint64_t* keys, int32_t* targets,
+                                   v3d_stream_t stream);
+
+/* rank [V + 1]: the exclusive scan of accept with its total.  done = min(total, Vcap - V_live, (Fcap - F_live) / 2) from counts_in [2];
+ * counts_out [2] = (V_live + done, F_live + 2 done) (two buffers); flag [1], cleared by the caller, = 1 when total > done: the accepted
+ * splits of rank >= done are dropped and nothing is written past a buffer.  For accepted a of rank r < done with editable (a, targets[a]):
+ * m = V_live + r gets 0.5 (p_a + p_b) and 0.5 (colour_a + colour_b);  (a, b, c) becomes (a, m, c) in place and (m, b, c) is written to face
+ * F_live + 2 r;  (b, a, d) becomes (b, m, d) in place and (m, a, d) is written to face F_live + 2 r + 1. */
+int v3d_recon_remesh_split_apply(float* verts, float* colors, int32_t num_verts, int32_t* faces, int32_t num_faces, const int32_t* ranges,
+                                 const int32_t* corners, const int32_t* accept, const int32_t* targets, const int32_t* rank,
+                                 const int32_t* counts_in, int32_t* counts_out, int32_t* flag, v3d_stream_t stream);
+
+/* Collapse v -> u, the half-edge collapse of "Mesh decimation" (u keeps its position and colour) under the rules of
+ * v3d_recon_mesh_decim_propose: v's faces are one closed fan of 3 .. max_valence, the link condition, the valence cap on u,
+ * n_before . n_after > 0 in fp64, no repeated face.  And: len^2(v, u) < lo^2, and no neighbour w of v other than u has len^2(u, w) > hi^2.
+ * Priority len^2: the shortest valid edge, the smaller u among equals; targets[v] = u. */
+int v3d_recon_remesh_collapse_propose(const float* verts, int32_t num_verts, const int32_t* faces, int32_t num_faces, const int32_t* ranges,
+                                      const int32_t* corners, float target_edge, int32_t max_valence, uint64_t* keys, int32_t* targets,
+                                      v3d_stream_t stream);
+
+/* For every accepted v: every face of v's list that holds targets[v] dies (Vcap Vcap Vcap), every other names targets[v] in v's place, in
+ * place; removed[v] = 1 (removed is otherwise left as it is). */
+int v3d_recon_remesh_collapse_apply(int32_t* faces, int32_t num_faces, int32_t num_verts, const int32_t* ranges, const int32_t* corners,
+                                    const int32_t* accept, const int32_t* targets, int32_t* removed, v3d_stream_t stream);
+
+/* Flip (a, b) -> (c, d).  The target valence t is 6, or 4 where boundary[x] != 0 (v3d_recon_mesh_boundary_flags).  a with 4 .. max_valence
+ * faces proposes an editable edge (a, b) when b has 4 .. max_valence faces, c and d have fewer than max_valence, c and d share no face (c's
+ * list is walked), gain = sum |val - t| over a, b, c, d now, minus the same with val(a) - 1, val(b) - 1, val(c) + 1, val(d) + 1, is
+ * positive, and both new faces (a, d, c) and (d, b, c) have n_new . n_old > 0 in fp64 with both old faces (a, b, c) and (b, a, d),
+ * n = (p1 - p0) x (p2 - p0).  The largest gain, the smaller b among equals; priority (float)(8 - gain); targets[a] = b. */
+int v3d_recon_remesh_flip_propose(const float* verts, int32_t num_verts, const int32_t* faces, int32_t num_faces, const int32_t* ranges,
+                                  const int32_t* corners, const int32_t* boundary, int32_t max_valence, uint64_t* keys, int32_t* targets,
+                                  v3d_stream_t stream);
+
+/* For every accepted a with editable (a, targets[a]): (a, b, c) becomes (a, d, c) and (b, a, d) becomes (d, b, c) (d takes b's place, c
+ * takes a's), in place. */
+int v3d_recon_remesh_flip_apply(int32_t* faces, int32_t num_faces, int32_t num_verts, const int32_t* ranges, const int32_t* corners,
+                                const int32_t* accept, const int32_t* targets, v3d_stream_t stream);
+
+/* verts_out [V][3] (two buffers): out = p + lambda (d - n (n . d)), d = the umbrella mean of v3d_recon_mesh_smooth_pass minus p, n = the sum of
+ * v3d_recon_mesh_vertex_normals divided by its length, n . d = (nx dx + ny dy) + nz dz.  The vertex is copied where boundary[v] != 0, where
+ * pinned[v] != 0 (pinned [V] or NULL), where it has no face and where the squared length of the normal sum is not above 1e-20.
+ * lambda in 0 .. 1. */
+int v3d_recon_remesh_relax(const float* verts_in, int32_t num_verts, const int32_t* faces, int32_t num_faces, const int32_t* ranges,
+                           const int32_t* corners, const int32_t* boundary, const int32_t* pinned, float lambda, float* verts_out,
+                           v3d_stream_t stream);
+
+/* hit_face [V], hit_uv [V][2]: what v3d_recon_bvh_closest_point answered for verts against the tree of the input mesh (src_verts, src_colors
+ * [Vs][3], src_faces [Fs][3]).  Per coordinate q = a + u (b - a) + v (c - a), but b itself where u == 1 and c itself where v == 1 (THE
+ * CLOSEST POINT OF A TRIANGLE), written to verts [V][3] in place; colors [V][3] likewise from the three colours.  A miss (hit_face outside
+ * 0 .. Fs-1, an absent face, u or v outside 0 .. 1) keeps the vertex and its colour. */
+int v3d_recon_remesh_project(const int32_t* hit_face, const float* hit_uv, const float* src_verts, const float* src_colors, int32_t src_num_verts,
+                             const int32_t* src_faces, int32_t src_num_faces, float* verts, float* colors, int32_t num_verts,
+                             v3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

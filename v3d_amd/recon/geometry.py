@@ -108,6 +108,15 @@ SIGNATURES = {
     "v3d_recon_tex_decode_tangent": (c_i32, [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp]),
     "v3d_recon_tex_shade_lit": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_f32, c_f32,
                                         c_f32, c_f32, c_vp, c_vp, c_vp]),
+    # mesh remeshing (csrc_recon/meshremesh.hip, v3d_amd/recon/mesh_remesh.py)
+    "v3d_recon_remesh_split_propose": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_f32, c_i32, c_vp, c_vp, c_vp]),
+    "v3d_recon_remesh_split_apply": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "v3d_recon_remesh_collapse_propose": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_f32, c_i32, c_vp, c_vp, c_vp]),
+    "v3d_recon_remesh_collapse_apply": (c_i32, [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "v3d_recon_remesh_flip_propose": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp]),
+    "v3d_recon_remesh_flip_apply": (c_i32, [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "v3d_recon_remesh_relax": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_f32, c_vp, c_vp]),
+    "v3d_recon_remesh_project": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_i32, c_vp]),
 }
 
 _lib = None

@@ -578,3 +578,32 @@ def proposals(name, op, dtype=np.float64, cap=DEFAULT_MAX_VALENCE):
 def excluded(margin):
     """the vertices whose decisions the comparison leaves out"""
     return [m <= NEAR for m in margin]
+
+
+# ---- against decimation ---------------------------------------------------------------------------------------------------------------------
+# The planted scenes of decimation whose normal tests all lie clear of 0 (tests/test_mesh_decimate_cpu.py), and a target edge that opens the
+# two length rules of the remeshing collapse wide: on these unit-scale scenes every edge is below 4/5 of it and none can come out above 4/3 of
+# it.  What is left of the remeshing rule is decimation's, so the two proposers must name the same proposing vertices.
+PLANTED = ("tetrahedron", "octahedron", "bipyramid", "dart", "grid")
+OPEN_WIDE = 1e3
+
+
+@functools.lru_cache(maxsize=None)
+def decimation_verdict(name, cap=DEFAULT_MAX_VALENCE):
+    """(keys, analysis) of mesh_decimate_ref on a planted scene, computed once"""
+    v, f, _ = Dm.scene(name)
+    faces = Dm.face_list(f)
+    Qv = Dm.vertex_quadrics(v, faces)
+    info = Dm.analyse(v, faces, Qv, cap)
+    return Dm.propose(v, faces, Qv, cap, info=info)[0], info
+
+
+def assert_collapse_proposers_agree(name, decim_keys, remesh_keys, remesh_targets, cap=DEFAULT_MAX_VALENCE):
+    """The same vertices propose in both, and every remeshing target is a collapse the decimation restatement calls valid"""
+    _, info = decimation_verdict(name, cap)
+    assert len(decim_keys) == len(remesh_keys) == len(remesh_targets) == len(info), name
+    assert [k != NO_KEY for k in remesh_keys] == [k != NO_KEY for k in decim_keys], name
+    for v, u in enumerate(remesh_targets):
+        assert (u == -1) == (remesh_keys[v] == NO_KEY), (name, v)
+        if u >= 0:
+            assert info[v] is not None and u in info[v] and not info[v][u]["why"], (name, v, u)

@@ -279,6 +279,22 @@ def test_premises_of_the_gpu_cases(name):
             assert got == (0, 0, 0)
 
 
+@pytest.mark.parametrize("name", Rm.PLANTED)
+def test_with_its_length_rules_open_wide_the_collapse_proposes_where_decimation_does(name):
+    """The two restatements against each other: nothing else holds the rule of one collapse to the rule of the other"""
+    v, f, c = Dm.scene(name)
+    cap = Rm.DEFAULT_MAX_VALENCE
+    decim_keys, info = Rm.decimation_verdict(name, cap)
+    st = Rm.State(v.numpy(), f.numpy(), c.numpy(), 0)
+    keys, targets, _ = Rm.collapse_propose(st, Rm.OPEN_WIDE, cap)
+    analysis = Rm.collapse_analyse(st, Rm.OPEN_WIDE, cap)
+    assert not any({"long", "stretch"} & c_["why"] for cand in analysis if cand for c_ in cand.values())          # the premise: both rules are open
+    Rm.assert_collapse_proposers_agree(name, decim_keys, keys, targets, cap)
+    proposing = sum(k != Rm.NO_KEY for k in keys)
+    print(f"{name}: {proposing} of {len(keys)} vertices propose in both")
+    assert proposing == {"tetrahedron": 0, "octahedron": 6, "bipyramid": 350, "dart": 1, "grid": int((~Dm.grid_rim()).sum())}[name]
+
+
 # ---- script and files -----------------------------------------------------------------------------------------------------------------------
 def _entry(name):
     spec = importlib.util.spec_from_file_location("v3d_entry_" + name, os.path.join(ROOT, "scripts", "pub", name + ".py"))

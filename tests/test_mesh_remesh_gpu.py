@@ -21,6 +21,7 @@ import mesh_decimate_ref as Dm
 import mesh_remesh_ref as Rm
 from conftest import record_parity
 from v3d_amd.recon import geometry as G
+from v3d_amd.recon import mesh_decimate as MD
 from v3d_amd.recon import mesh_remesh as MR
 
 pytestmark = pytest.mark.gpu
@@ -181,6 +182,19 @@ def test_propose_select_and_apply_are_the_restatements(name):
         assert figures["split"]["proposals"] == 0
     if name == "bipyramid":
         assert figures["split"]["proposals"] == 350
+
+
+@pytest.mark.parametrize("name", Rm.PLANTED)
+def test_with_its_length_rules_open_wide_the_collapse_kernel_proposes_where_the_decimation_kernel_does(name):
+    """The two propose kernels against each other (and the remeshing targets against the decimation restatement): the closed-fan walk and the
+    integer rules are one piece of code, the normal tests are each kernel's own, and on these scenes no normal test is near its threshold"""
+    v, f, c = Dm.scene(name)
+    cap = Rm.DEFAULT_MAX_VALENCE
+    decim_keys, _ = MD.propose(v, f, MD.vertex_quadrics(v, f), max_valence=cap)
+    st = MR.RemeshState(v.to(DEV), f.to(DEV).to(torch.int32), c.to(DEV), 0)
+    keys, targets = MR.collapse_propose(st, Rm.OPEN_WIDE, cap)
+    Rm.assert_collapse_proposers_agree(name, unsigned(decim_keys), unsigned(keys), targets.tolist(), cap)
+    print(f"{name}: {sum(k != NO_KEY for k in unsigned(keys))} of {v.shape[0]} vertices propose in both kernels")
 
 
 def test_a_capacity_one_vertex_short_drops_by_rank_and_writes_nothing_past_it():

@@ -1,15 +1,15 @@
 // Isotropic remeshing of the mesh (include/v3d_recon.h "Mesh remeshing", libv3d_recon.so; host side: v3d_amd/recon/mesh_remesh.py): edge
 // split, half-edge collapse and edge flip towards a target edge length L (Botsch & Kobbelt 2004: split above 4/3 L, collapse below 4/5 L,
 // flip towards valence 6), tangential relaxation and reprojection onto the input mesh.  Every topological operation is proposed by a vertex
-// on its own corner list (meshtopo.hip, rebuilt per round from the live faces by the host) as a 64-bit key; the selection is meshdecim.hip's
+// on its own corner list (mesh_lists.h, rebuilt per round from the live faces by the host) as a 64-bit key; the selection is meshdecim.hip's
 // (min_round twice, accept), which leaves accepted vertices at least 3 edges apart; the apply kernels, one thread per vertex, then write only
 // faces that hold the accepted vertex itself, in place.
 //
 // No atomics: every output element has one owner.  Lists are short (a vertex above the valence cap proposes nothing), so a thread re-walks
 // them instead of keeping them: no local arrays, no LDS.  Positions are float32; lengths are float32, (dx dx + dy dy) + dz dz, the normal
 // tests are fp64, without contraction, statement for statement as tests/mesh_remesh_ref.py writes them.  A dead or unborn face holds
-// num_verts in all three places: like any face with an index outside 0 .. V-1 it is absent everywhere.  The closed-fan walk and the validity
-// rules of the collapse are those of meshdecim.hip, restated here.
+// num_verts in all three places: like any face with an index outside 0 .. V-1 it is absent everywhere.  The closed-fan walk and the integer
+// rules of the collapse are meshdecim.hip's own: both call closed_fan and collapse_topology_ok of mesh_lists.h.
 //
 // The library is built with -ffast-math ... -fno-fast-math, which leaves -ffp-contract=fast behind: the pragma below states the intent but the
 // compiler does not honour it, and a product that feeds a sum would be fused into an fma.  Every such product therefore goes through mul(),
@@ -18,6 +18,7 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "mesh_lists.h"
 #include "recon_host.h"
 #include "v3d_recon.h"
 
@@ -25,89 +26,11 @@
 
 namespace {
 
-constexpr unsigned long long NO_KEY = ~0ull;
 constexpr unsigned KEY_HASH = 0x9E3779B1u;                    // odd: v -> v * KEY_HASH mod 2^32 is a bijection, so keys stay distinct
-
-__device__ __forceinline__ bool in_range(int i, int n) { return i >= 0 && i < n; }
-
-__device__ __forceinline__ bool load_face(const int32_t* faces, long long f, int nv, int& i0, int& i1, int& i2) {
-    i0 = faces[3 * f];
-    i1 = faces[3 * f + 1];
-    i2 = faces[3 * f + 2];
-    return in_range(i0, nv) && in_range(i1, nv) && in_range(i2, nv);
-}
-
-// Corner (k + s) % 3 of a face, without an indexed array
-__device__ __forceinline__ int corner_at(int k, int s, int i0, int i1, int i2) {
-    const int j = (k + s) % 3;
-    return j == 0 ? i0 : (j == 1 ? i1 : i2);
-}
 
 __device__ __forceinline__ unsigned long long make_key(unsigned bits, int v) {
     return ((unsigned long long)bits << 32) | (unsigned long long)((unsigned)v * KEY_HASH);
 }
-
-// The walk over one vertex's list: entry i gives the face's three vertices, the corner's place k, and the two neighbours a = next, b = prev.
-// (faces is not __restrict__: the apply kernels write the faces they have read through it)
-struct Lists {
-    const int32_t* faces;
-    const int32_t* __restrict__ ranges;
-    const int32_t* __restrict__ corners;
-    int nf, nv;
-
-    __device__ __forceinline__ void range(long long v, int& start, int& end) const {
-        start = max(ranges[2 * v], 0);
-        end = (int)min((long long)ranges[2 * v + 1], 3LL * nf);
-    }
-    __device__ __forceinline__ bool entry(int i, int& k, int& i0, int& i1, int& i2) const {
-        const long long c = corners[i];
-        if (c < 0 || c >= 3LL * nf) return false;
-        k = (int)(c % 3);
-        return load_face(faces, c / 3, nv, i0, i1, i2);
-    }
-    __device__ __forceinline__ bool neighbours(int i, int& a, int& b) const {
-        int k, i0, i1, i2;
-        if (!entry(i, k, i0, i1, i2)) return false;
-        a = corner_at(k, 1, i0, i1, i2);
-        b = corner_at(k, 2, i0, i1, i2);
-        return true;
-    }
-    // present entries of the list, counted up to limit + 1
-    __device__ __forceinline__ int count(int start, int end, int limit) const {
-        int n = 0;
-        for (int i = start; i < end && n <= limit; ++i) {
-            int a, b;
-            n += neighbours(i, a, b) ? 1 : 0;
-        }
-        return n;
-    }
-    __device__ __forceinline__ int valence(int v, int limit) const {
-        int s, e;
-        range(v, s, e);
-        return count(s, e, limit);
-    }
-    // The edge (a, b) from a's list [start, end): editable when exactly one entry has b next (the face a b c, entry ic) and exactly one has b
-    // before a (the face b a d, entry id), and a, b, c, d are four vertices
-    __device__ __forceinline__ bool editable(int a, int start, int end, int b, int& ic, int& c, int& id, int& d) const {
-        int nab = 0, nba = 0;
-        ic = id = c = d = -1;
-        for (int i = start; i < end; ++i) {
-            int x, y;
-            if (!neighbours(i, x, y)) continue;
-            if (x == b) {
-                ++nab;
-                ic = i;
-                c = y;
-            }
-            if (y == b) {
-                ++nba;
-                id = i;
-                d = x;
-            }
-        }
-        return nab == 1 && nba == 1 && b != a && c != d && c != a && d != a && c != b && d != b;
-    }
-};
 
 // a b, rounded on its own: the empty asm keeps the product out of any fused multiply-add
 __device__ __forceinline__ float mul(float a, float b) {
@@ -119,14 +42,6 @@ __device__ __forceinline__ double mul(double a, double b) {
     double p = a * b;
     asm("" : "+v"(p));
     return p;
-}
-
-struct D3 {
-    double x, y, z;
-};
-
-__device__ __forceinline__ D3 load_pos(const float* __restrict__ verts, long long i) {
-    return D3{(double)verts[3 * i], (double)verts[3 * i + 1], (double)verts[3 * i + 2]};
 }
 
 // (p1 - p0) x (p2 - p0)
@@ -221,30 +136,12 @@ __global__ void __launch_bounds__(NT) remesh_split_apply_kernel(float* __restric
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------------
-// Collapse v -> u.  Is it valid, given that v's star [start, end) is one closed fan of n_v faces?  i_u: the entry whose next neighbour is u.
-__device__ bool collapse_valid(const float* __restrict__ verts, const Lists& L, int v, int start, int end, int n_v, int u, int i_u, int max_valence,
-                               float hi2) {
-    int a1, a2 = -1, t;
-    L.neighbours(i_u, t, a1);                                 // the face (v, u, a1)
-    for (int j = start; j < end; ++j) {                       // the face (v, a2, u)
-        int a, b;
-        if (L.neighbours(j, a, b) && b == u) a2 = a;
-    }
-    if (a2 < 0 || a1 == a2) return false;
-    int us, ue;
-    L.range(u, us, ue);
-    const int room = max_valence + 4 - n_v;                   // u ends with n_u + n_v - 4 faces
-    if (L.count(us, ue, room) > room) return false;
-    // the link condition: no neighbour of v other than the two apexes is a neighbour of u; and no edge (u, w) may come out longer than hi
+// Collapse v -> u.  The geometric half of its validity (the integer half is mesh_lists.h's collapse_topology_ok), over v's star [start, end):
+// no edge (u, w) may come out longer than hi, and every face that survives keeps its side.
+__device__ bool collapse_keeps_shape(const float* __restrict__ verts, const Lists& L, int start, int end, int u, float hi2) {
     for (int j = start; j < end; ++j) {
         int w, b;
-        if (!L.neighbours(j, w, b) || w == u) continue;
-        if (dist2(verts, u, w) > hi2) return false;
-        if (w == a1 || w == a2) continue;
-        for (int m = us; m < ue; ++m) {
-            int x, y;
-            if (L.neighbours(m, x, y) && (x == w || y == w)) return false;
-        }
+        if (L.neighbours(j, w, b) && w != u && dist2(verts, u, w) > hi2) return false;
     }
     const D3 pu = load_pos(verts, u);
     for (int j = start; j < end; ++j) {                       // the faces that survive: v's faces without u
@@ -256,10 +153,6 @@ __device__ bool collapse_valid(const float* __restrict__ verts, const Lists& L, 
         const D3 before = face_cross(p0, p1, p2);
         const D3 after = face_cross(k == 0 ? pu : p0, k == 1 ? pu : p1, k == 2 ? pu : p2);
         if (!(dot(before, after) > 0.0)) return false;        // flipped, or without area before or after
-        for (int m = us; m < ue; ++m) {                       // u already has a face on these three vertices
-            int x, y;
-            if (L.neighbours(m, x, y) && ((x == a && y == b) || (x == b && y == a))) return false;
-        }
     }
     return true;
 }
@@ -274,51 +167,15 @@ __global__ void __launch_bounds__(NT) remesh_collapse_propose_kernel(const float
     int start, end;
     L.range(v, start, end);
     const int n_v = L.count(start, end, max_valence);
-    bool removable = n_v >= 3 && n_v <= max_valence;
-    // a closed fan: every neighbour is the next corner of one entry and the previous corner of one entry ..
-    for (int i = start; i < end && removable; ++i) {
-        int a, b;
-        if (!L.neighbours(i, a, b)) continue;
-        if (a == v || b == v || a == b) removable = false;
-        int na = 0, pa = 0, nb = 0, pb = 0;
-        for (int j = start; j < end; ++j) {
-            int x, y;
-            if (!L.neighbours(j, x, y)) continue;
-            na += x == a;
-            pa += y == a;
-            nb += x == b;
-            pb += y == b;
-        }
-        removable = removable && na == 1 && pa == 1 && nb == 1 && pb == 1;
-    }
-    // .. and one fan, not several that meet at v: stepping from an entry to the one that starts where it ends comes round after n_v steps
-    if (removable) {
-        int first = -1, x = -1, steps = 0;
-        for (int i = start; i < end && first < 0; ++i) {
-            int a, b;
-            if (L.neighbours(i, a, b)) {
-                first = a;
-                x = b;
-            }
-        }
-        for (steps = 1; steps <= n_v && x != first; ++steps) {
-            int nx = first;
-            for (int j = start; j < end; ++j) {
-                int a, b;
-                if (L.neighbours(j, a, b) && a == x) nx = b;
-            }
-            x = nx;
-        }
-        removable = steps == n_v;
-    }
-    if (removable) {
+    if (n_v >= 3 && n_v <= max_valence && closed_fan(L, v, start, end, n_v)) {
         unsigned best_bits = 0xffffffffu;
         for (int i = start; i < end; ++i) {
             int u, b;
             if (!L.neighbours(i, u, b)) continue;
             const float len2 = dist2(verts, v, u);
             if (!(len2 < lo2)) continue;
-            if (!collapse_valid(verts, L, v, start, end, n_v, u, i, max_valence, hi2)) continue;
+            // (the geometric half first, as in meshdecim.hip and for its reason: the length cap turns most candidates down after a few loads)
+            if (!(collapse_keeps_shape(verts, L, start, end, u, hi2) && collapse_topology_ok(L, v, start, end, n_v, u, i, max_valence))) continue;
             const unsigned bits = __float_as_uint(len2);
             if (target < 0 || bits < best_bits || (bits == best_bits && u < target)) {
                 best_bits = bits;
@@ -495,26 +352,19 @@ __global__ void __launch_bounds__(NT) remesh_project_kernel(const int32_t* __res
     }
 }
 
-bool counts_ok(int32_t nv, int32_t nf) { return nv > 0 && nf > 0 && nf <= INT32_MAX / 3; }
 bool edge_ok(float e) { return e > 0.f && e < INFINITY; }
 
 }  // namespace
 
-#define ST ((hipStream_t)stream)
-#define REMESH_REQUIRE_COUNTS(name, nv, nf)                                                                                            \
-    RECON_REQUIRE(counts_ok(nv, nf), name ": num_verts %d and num_faces %d must be positive, 3 x num_faces at most INT32_MAX", (int)(nv), \
-                  (int)(nf))
-#define REMESH_REQUIRE_VALENCE(name, m) \
-    RECON_REQUIRE((m) >= 3 && (m) <= V3D_RECON_MESH_MAX_VALENCE, name ": max_valence %d outside 3 .. %d", (int)(m), V3D_RECON_MESH_MAX_VALENCE)
 #define REMESH_REQUIRE_EDGE(name, e) RECON_REQUIRE(edge_ok(e), name ": target_edge %g must be positive and finite", (double)(e))
 
 extern "C" int v3d_recon_remesh_split_propose(const float* verts, int32_t num_verts, const int32_t* faces, int32_t num_faces, const int32_t* ranges,
                                               const int32_t* corners, float target_edge, int32_t max_valence, uint64_t* keys, int32_t* targets,
                                               v3d_stream_t stream) {
     RECON_REQUIRE(verts && faces && ranges && corners && keys && targets, "v3d_recon_remesh_split_propose: null argument");
-    REMESH_REQUIRE_COUNTS("v3d_recon_remesh_split_propose", num_verts, num_faces);
+    MESH_REQUIRE_COUNTS("v3d_recon_remesh_split_propose", num_verts, num_faces);
     REMESH_REQUIRE_EDGE("v3d_recon_remesh_split_propose", target_edge);
-    REMESH_REQUIRE_VALENCE("v3d_recon_remesh_split_propose", max_valence);
+    MESH_REQUIRE_VALENCE("v3d_recon_remesh_split_propose", max_valence);
     const Lists L{faces, ranges, corners, (int)num_faces, (int)num_verts};
     const float L2 = target_edge * target_edge, hi2 = (16.f / 9.f) * L2;
     hipLaunchKernelGGL(remesh_split_propose_kernel, dim3(nblk(num_verts)), dim3(NT), 0, ST, verts, L, L2, hi2, (int)max_valence,
@@ -528,7 +378,7 @@ extern "C" int v3d_recon_remesh_split_apply(float* verts, float* colors, int32_t
     RECON_REQUIRE(verts && colors && faces && ranges && corners && accept && targets && rank && counts_in && counts_out && flag,
                   "v3d_recon_remesh_split_apply: null argument");
     RECON_REQUIRE(counts_in != counts_out, "v3d_recon_remesh_split_apply: counts_in and counts_out must be two buffers");
-    REMESH_REQUIRE_COUNTS("v3d_recon_remesh_split_apply", num_verts, num_faces);
+    MESH_REQUIRE_COUNTS("v3d_recon_remesh_split_apply", num_verts, num_faces);
     const Lists L{faces, ranges, corners, (int)num_faces, (int)num_verts};
     hipLaunchKernelGGL(remesh_split_apply_kernel, dim3(nblk(num_verts)), dim3(NT), 0, ST, verts, colors, faces, L, accept, targets, rank, counts_in,
                        counts_out, flag);
@@ -539,9 +389,9 @@ extern "C" int v3d_recon_remesh_collapse_propose(const float* verts, int32_t num
                                                  const int32_t* corners, float target_edge, int32_t max_valence, uint64_t* keys, int32_t* targets,
                                                  v3d_stream_t stream) {
     RECON_REQUIRE(verts && faces && ranges && corners && keys && targets, "v3d_recon_remesh_collapse_propose: null argument");
-    REMESH_REQUIRE_COUNTS("v3d_recon_remesh_collapse_propose", num_verts, num_faces);
+    MESH_REQUIRE_COUNTS("v3d_recon_remesh_collapse_propose", num_verts, num_faces);
     REMESH_REQUIRE_EDGE("v3d_recon_remesh_collapse_propose", target_edge);
-    REMESH_REQUIRE_VALENCE("v3d_recon_remesh_collapse_propose", max_valence);
+    MESH_REQUIRE_VALENCE("v3d_recon_remesh_collapse_propose", max_valence);
     const Lists L{faces, ranges, corners, (int)num_faces, (int)num_verts};
     const float L2 = target_edge * target_edge, lo2 = (16.f / 25.f) * L2, hi2 = (16.f / 9.f) * L2;
     hipLaunchKernelGGL(remesh_collapse_propose_kernel, dim3(nblk(num_verts)), dim3(NT), 0, ST, verts, L, lo2, hi2, (int)max_valence,
@@ -552,7 +402,7 @@ extern "C" int v3d_recon_remesh_collapse_propose(const float* verts, int32_t num
 extern "C" int v3d_recon_remesh_collapse_apply(int32_t* faces, int32_t num_faces, int32_t num_verts, const int32_t* ranges, const int32_t* corners,
                                                const int32_t* accept, const int32_t* targets, int32_t* removed, v3d_stream_t stream) {
     RECON_REQUIRE(faces && ranges && corners && accept && targets && removed, "v3d_recon_remesh_collapse_apply: null argument");
-    REMESH_REQUIRE_COUNTS("v3d_recon_remesh_collapse_apply", num_verts, num_faces);
+    MESH_REQUIRE_COUNTS("v3d_recon_remesh_collapse_apply", num_verts, num_faces);
     const Lists L{faces, ranges, corners, (int)num_faces, (int)num_verts};
     hipLaunchKernelGGL(remesh_collapse_apply_kernel, dim3(nblk(num_verts)), dim3(NT), 0, ST, faces, L, accept, targets, removed);
     return check_launch("v3d_recon_remesh_collapse_apply");
@@ -562,8 +412,8 @@ extern "C" int v3d_recon_remesh_flip_propose(const float* verts, int32_t num_ver
                                              const int32_t* corners, const int32_t* boundary, int32_t max_valence, uint64_t* keys, int32_t* targets,
                                              v3d_stream_t stream) {
     RECON_REQUIRE(verts && faces && ranges && corners && boundary && keys && targets, "v3d_recon_remesh_flip_propose: null argument");
-    REMESH_REQUIRE_COUNTS("v3d_recon_remesh_flip_propose", num_verts, num_faces);
-    REMESH_REQUIRE_VALENCE("v3d_recon_remesh_flip_propose", max_valence);
+    MESH_REQUIRE_COUNTS("v3d_recon_remesh_flip_propose", num_verts, num_faces);
+    MESH_REQUIRE_VALENCE("v3d_recon_remesh_flip_propose", max_valence);
     const Lists L{faces, ranges, corners, (int)num_faces, (int)num_verts};
     hipLaunchKernelGGL(remesh_flip_propose_kernel, dim3(nblk(num_verts)), dim3(NT), 0, ST, verts, L, boundary, (int)max_valence,
                        (unsigned long long*)keys, targets);
@@ -573,7 +423,7 @@ extern "C" int v3d_recon_remesh_flip_propose(const float* verts, int32_t num_ver
 extern "C" int v3d_recon_remesh_flip_apply(int32_t* faces, int32_t num_faces, int32_t num_verts, const int32_t* ranges, const int32_t* corners,
                                            const int32_t* accept, const int32_t* targets, v3d_stream_t stream) {
     RECON_REQUIRE(faces && ranges && corners && accept && targets, "v3d_recon_remesh_flip_apply: null argument");
-    REMESH_REQUIRE_COUNTS("v3d_recon_remesh_flip_apply", num_verts, num_faces);
+    MESH_REQUIRE_COUNTS("v3d_recon_remesh_flip_apply", num_verts, num_faces);
     const Lists L{faces, ranges, corners, (int)num_faces, (int)num_verts};
     hipLaunchKernelGGL(remesh_flip_apply_kernel, dim3(nblk(num_verts)), dim3(NT), 0, ST, faces, L, accept, targets);
     return check_launch("v3d_recon_remesh_flip_apply");
@@ -584,7 +434,7 @@ extern "C" int v3d_recon_remesh_relax(const float* verts_in, int32_t num_verts, 
                                       v3d_stream_t stream) {
     RECON_REQUIRE(verts_in && faces && ranges && corners && boundary && verts_out, "v3d_recon_remesh_relax: null argument");
     RECON_REQUIRE(verts_in != verts_out, "v3d_recon_remesh_relax: verts_in and verts_out must be two buffers");
-    REMESH_REQUIRE_COUNTS("v3d_recon_remesh_relax", num_verts, num_faces);
+    MESH_REQUIRE_COUNTS("v3d_recon_remesh_relax", num_verts, num_faces);
     RECON_REQUIRE(lambda >= 0.f && lambda <= 1.f, "v3d_recon_remesh_relax: lambda %g outside 0 .. 1", (double)lambda);
     const Lists L{faces, ranges, corners, (int)num_faces, (int)num_verts};
     hipLaunchKernelGGL(remesh_relax_kernel, dim3(nblk(num_verts)), dim3(NT), 0, ST, verts_in, L, boundary, pinned, lambda, verts_out);
@@ -595,7 +445,7 @@ extern "C" int v3d_recon_remesh_project(const int32_t* hit_face, const float* hi
                                         int32_t src_num_verts, const int32_t* src_faces, int32_t src_num_faces, float* verts, float* colors,
                                         int32_t num_verts, v3d_stream_t stream) {
     RECON_REQUIRE(hit_face && hit_uv && src_verts && src_colors && src_faces && verts && colors, "v3d_recon_remesh_project: null argument");
-    REMESH_REQUIRE_COUNTS("v3d_recon_remesh_project", src_num_verts, src_num_faces);
+    MESH_REQUIRE_COUNTS("v3d_recon_remesh_project", src_num_verts, src_num_faces);
     RECON_REQUIRE(num_verts > 0, "v3d_recon_remesh_project: num_verts %d must be positive", (int)num_verts);
     RECON_REQUIRE(verts != src_verts && colors != src_colors, "v3d_recon_remesh_project: the input mesh and the vertices must be two buffers");
     hipLaunchKernelGGL(remesh_project_kernel, dim3(nblk(num_verts)), dim3(NT), 0, ST, hit_face, hit_uv, src_verts, src_colors, (int)src_num_verts,

@@ -2,7 +2,8 @@
 // vertex -> incident-corner lists, and what walks them: area-weighted vertex normals, connected components by min-label propagation with one
 // pointer jump per round, the flags and the index remap of the component filter, open-edge (boundary) flags and one pass of umbrella
 // smoothing.  The lists come from corner_records -> v3d_gs_radix_sort_pairs -> v3d_recon_mesh_vertex_ranges (meshshade.hip); the scans and the
-// sorts are libv3d_hip.so's, called by the host.
+// sorts are libv3d_hip.so's, called by the host.  The walk itself (struct Lists) is mesh_lists.h's, shared with meshdecim.hip and
+// meshremesh.hip.
 //
 // No atomics: every output element belongs to one thread, which walks its vertex's list in list order (ascending corner index, the sort is
 // stable), so every sum has one order and two runs are bit-equal.  Lists are short (valence 4 - 10 on what surface nets produce): one thread
@@ -13,43 +14,13 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "mesh_lists.h"
 #include "recon_host.h"
 #include "v3d_recon.h"
 
 #pragma clang fp contract(off)
 
 namespace {
-
-__device__ __forceinline__ bool in_range(int i, int n) { return i >= 0 && i < n; }
-
-// The three vertices of face f; false when one of them lies outside 0 .. nv-1 (the face is then absent)
-__device__ __forceinline__ bool load_face(const int32_t* __restrict__ faces, long long f, int nv, int& i0, int& i1, int& i2) {
-    i0 = faces[3 * f];
-    i1 = faces[3 * f + 1];
-    i2 = faces[3 * f + 2];
-    return in_range(i0, nv) && in_range(i1, nv) && in_range(i2, nv);
-}
-
-// Entry i of a list: the face of corner corners[i] and the corner's place k in it; false for a corner outside 0 .. 3F-1 or an absent face
-__device__ __forceinline__ bool list_face(const int32_t* __restrict__ corners, int i, const int32_t* __restrict__ faces, int nf, int nv, int& k,
-                                          int& i0, int& i1, int& i2) {
-    const long long c = corners[i];
-    if (c < 0 || c >= 3LL * nf) return false;
-    k = (int)(c % 3);
-    return load_face(faces, c / 3, nv, i0, i1, i2);
-}
-
-// Corner (k + s) % 3 of a face, without an indexed array
-__device__ __forceinline__ int corner_at(int k, int s, int i0, int i1, int i2) {
-    const int j = (k + s) % 3;
-    return j == 0 ? i0 : (j == 1 ? i1 : i2);
-}
-
-// The clamped [start, end) of vertex v's list
-__device__ __forceinline__ void list_range(const int32_t* __restrict__ ranges, long long v, long long n, int& start, int& end) {
-    start = max(ranges[2 * v], 0);
-    end = (int)min((long long)ranges[2 * v + 1], n);
-}
 
 // ---------------------------------------------------------------------------------------------------------------------------------------
 // Three records per face in face order: the stable sort on the vertex leaves every vertex's corners in ascending 3 f + k.  A record whose
@@ -64,17 +35,15 @@ __global__ void __launch_bounds__(NT) mesh_corner_records_kernel(const int32_t* 
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(NT) mesh_vertex_normals_kernel(const float* __restrict__ verts, int nv, const int32_t* __restrict__ faces, int nf,
-                                                                 const int32_t* __restrict__ ranges, const int32_t* __restrict__ corners,
-                                                                 float* __restrict__ normals) {
+__global__ void __launch_bounds__(NT) mesh_vertex_normals_kernel(const float* __restrict__ verts, Lists L, float* __restrict__ normals) {
     const long long v = (long long)blockIdx.x * NT + threadIdx.x;
-    if (v >= nv) return;
+    if (v >= L.nv) return;
     int start, end;
-    list_range(ranges, v, 3LL * nf, start, end);
+    L.range(v, start, end);
     float nx = 0.f, ny = 0.f, nz = 0.f;
     for (int i = start; i < end; ++i) {
         int k, i0, i1, i2;
-        if (!list_face(corners, i, faces, nf, nv, k, i0, i1, i2)) continue;
+        if (!L.entry(i, k, i0, i1, i2)) continue;
         const float ax = verts[3 * (long long)i0], ay = verts[3 * (long long)i0 + 1], az = verts[3 * (long long)i0 + 2];
         const float ux = verts[3 * (long long)i1] - ax, uy = verts[3 * (long long)i1 + 1] - ay, uz = verts[3 * (long long)i1 + 2] - az;
         const float wx = verts[3 * (long long)i2] - ax, wy = verts[3 * (long long)i2 + 1] - ay, wz = verts[3 * (long long)i2 + 2] - az;
@@ -101,21 +70,20 @@ __global__ void __launch_bounds__(NT) mesh_vertex_normals_kernel(const float* __
 // ---------------------------------------------------------------------------------------------------------------------------------------
 // One round of the labelling.  labels_in is read-only for the whole launch and labels_out has one owner per element, so the result does not
 // depend on the order in which threads run.  Labels only ever fall, and stay inside the component: labels[x] <= x names a vertex joined to x.
-__global__ void __launch_bounds__(NT) mesh_label_round_kernel(const int32_t* __restrict__ faces, int nf, const int32_t* __restrict__ ranges,
-                                                              const int32_t* __restrict__ corners, int nv, const int32_t* __restrict__ labels_in,
-                                                              int32_t* __restrict__ labels_out, int32_t* __restrict__ changed) {
+__global__ void __launch_bounds__(NT) mesh_label_round_kernel(Lists L, const int32_t* __restrict__ labels_in, int32_t* __restrict__ labels_out,
+                                                              int32_t* __restrict__ changed) {
     const long long v = (long long)blockIdx.x * NT + threadIdx.x;
-    if (v >= nv) return;
+    if (v >= L.nv) return;
     int start, end;
-    list_range(ranges, v, 3LL * nf, start, end);
+    L.range(v, start, end);
     const int mine = labels_in[v];
     int m = mine;
     for (int i = start; i < end; ++i) {
         int k, i0, i1, i2;
-        if (!list_face(corners, i, faces, nf, nv, k, i0, i1, i2)) continue;
+        if (!L.entry(i, k, i0, i1, i2)) continue;
         m = min(m, min(labels_in[i0], min(labels_in[i1], labels_in[i2])));
     }
-    const int out = in_range(m, nv) ? labels_in[m] : mine;                // the jump (labels[m] <= m on labels this pass made)
+    const int out = in_range(m, L.nv) ? labels_in[m] : mine;              // the jump (labels[m] <= m on labels this pass made)
     labels_out[v] = out;
     if (out != mine) *changed = 1;                                        // (every writer stores the same value)
 }
@@ -137,28 +105,26 @@ __global__ void __launch_bounds__(NT) mesh_face_labels_kernel(const int32_t* __r
 
 // ---------------------------------------------------------------------------------------------------------------------------------------
 // Thread t decides face t (t < nf) and vertex t (t < nv)
-__global__ void __launch_bounds__(NT) mesh_keep_flags_kernel(const int32_t* __restrict__ faces, int nf, const int32_t* __restrict__ ranges,
-                                                             const int32_t* __restrict__ corners, int nv, const int32_t* __restrict__ labels,
-                                                             const int32_t* __restrict__ keep_root, int32_t* __restrict__ keep_face,
-                                                             int32_t* __restrict__ keep_vert) {
+__global__ void __launch_bounds__(NT) mesh_keep_flags_kernel(Lists L, const int32_t* __restrict__ labels, const int32_t* __restrict__ keep_root,
+                                                             int32_t* __restrict__ keep_face, int32_t* __restrict__ keep_vert) {
     const long long t = (long long)blockIdx.x * NT + threadIdx.x;
-    if (t < nf) {
+    if (t < L.nf) {
         int i0, i1, i2, keep = 0;
-        if (load_face(faces, t, nv, i0, i1, i2)) {
+        if (load_face(L.faces, t, L.nv, i0, i1, i2)) {
             const int l = labels[i0];
-            keep = in_range(l, nv) && keep_root[l] != 0;
+            keep = in_range(l, L.nv) && keep_root[l] != 0;
         }
         keep_face[t] = keep;
     }
-    if (t < nv) {
+    if (t < L.nv) {
         const int l = labels[t];
         int keep = 0;
-        if (in_range(l, nv) && keep_root[l] != 0) {
+        if (in_range(l, L.nv) && keep_root[l] != 0) {
             int start, end;
-            list_range(ranges, t, 3LL * nf, start, end);
+            L.range(t, start, end);
             for (int i = start; i < end && !keep; ++i) {
                 int k, i0, i1, i2;
-                keep = list_face(corners, i, faces, nf, nv, k, i0, i1, i2);
+                keep = L.entry(i, k, i0, i1, i2);
             }
         }
         keep_vert[t] = keep;
@@ -185,23 +151,22 @@ __global__ void __launch_bounds__(NT) mesh_compact_faces_kernel(const int32_t* _
 // ---------------------------------------------------------------------------------------------------------------------------------------
 // An entry of v's list at corner k has the neighbours faces[f][(k + 1) % 3] and faces[f][(k + 2) % 3].  v lies on an open edge when some
 // neighbour other than v is a neighbour in exactly one entry.  Quadratic in the list length, which is 4 - 10 here.
-__global__ void __launch_bounds__(NT) mesh_boundary_flags_kernel(const int32_t* __restrict__ faces, int nf, const int32_t* __restrict__ ranges,
-                                                                 const int32_t* __restrict__ corners, int nv, int32_t* __restrict__ flags) {
+__global__ void __launch_bounds__(NT) mesh_boundary_flags_kernel(Lists L, int32_t* __restrict__ flags) {
     const long long v = (long long)blockIdx.x * NT + threadIdx.x;
-    if (v >= nv) return;
+    if (v >= L.nv) return;
     int start, end;
-    list_range(ranges, v, 3LL * nf, start, end);
+    L.range(v, start, end);
     int open = 0;
     for (int i = start; i < end && !open; ++i) {
         int k, i0, i1, i2;
-        if (!list_face(corners, i, faces, nf, nv, k, i0, i1, i2)) continue;
+        if (!L.entry(i, k, i0, i1, i2)) continue;
         for (int s = 1; s <= 2 && !open; ++s) {
             const int u = corner_at(k, s, i0, i1, i2);
             if (u == v) continue;
             int count = 0;
             for (int j = start; j < end && count < 2; ++j) {
                 int kj, j0, j1, j2;
-                if (!list_face(corners, j, faces, nf, nv, kj, j0, j1, j2)) continue;
+                if (!L.entry(j, kj, j0, j1, j2)) continue;
                 count += (corner_at(kj, 1, j0, j1, j2) == u || corner_at(kj, 2, j0, j1, j2) == u) ? 1 : 0;
             }
             open = count == 1;
@@ -211,21 +176,20 @@ __global__ void __launch_bounds__(NT) mesh_boundary_flags_kernel(const int32_t* 
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(NT) mesh_smooth_pass_kernel(const float* __restrict__ verts_in, int nv, const int32_t* __restrict__ faces, int nf,
-                                                              const int32_t* __restrict__ ranges, const int32_t* __restrict__ corners,
-                                                              const int32_t* __restrict__ pinned, float factor, float* __restrict__ verts_out) {
+__global__ void __launch_bounds__(NT) mesh_smooth_pass_kernel(const float* __restrict__ verts_in, Lists L, const int32_t* __restrict__ pinned,
+                                                              float factor, float* __restrict__ verts_out) {
     const long long v = (long long)blockIdx.x * NT + threadIdx.x;
-    if (v >= nv) return;
+    if (v >= L.nv) return;
     const float px = verts_in[3 * v], py = verts_in[3 * v + 1], pz = verts_in[3 * v + 2];
     float ox = px, oy = py, oz = pz;
     if (pinned == nullptr || pinned[v] == 0) {
         int start, end;
-        list_range(ranges, v, 3LL * nf, start, end);
+        L.range(v, start, end);
         float sx = 0.f, sy = 0.f, sz = 0.f;
         int count = 0;
         for (int i = start; i < end; ++i) {
             int k, i0, i1, i2;
-            if (!list_face(corners, i, faces, nf, nv, k, i0, i1, i2)) continue;
+            if (!L.entry(i, k, i0, i1, i2)) continue;
             const long long a = corner_at(k, 1, i0, i1, i2), b = corner_at(k, 2, i0, i1, i2);
             sx += 0.5f * (verts_in[3 * a] + verts_in[3 * b]);
             sy += 0.5f * (verts_in[3 * a + 1] + verts_in[3 * b + 1]);
@@ -244,19 +208,12 @@ __global__ void __launch_bounds__(NT) mesh_smooth_pass_kernel(const float* __res
     verts_out[3 * v + 2] = oz;
 }
 
-bool counts_ok(int32_t nv, int32_t nf) { return nv > 0 && nf > 0 && nf <= INT32_MAX / 3; }
-
 }  // namespace
-
-#define ST ((hipStream_t)stream)
-#define TOPO_REQUIRE_COUNTS(name, nv, nf)                                                                                              \
-    RECON_REQUIRE(counts_ok(nv, nf), name ": num_verts %d and num_faces %d must be positive, 3 x num_faces at most INT32_MAX", (int)(nv), \
-                  (int)(nf))
 
 extern "C" int v3d_recon_mesh_corner_records(const int32_t* faces, int32_t num_faces, int32_t num_verts, uint64_t* keys, uint32_t* vals,
                                              v3d_stream_t stream) {
     RECON_REQUIRE(faces && keys && vals, "v3d_recon_mesh_corner_records: null argument");
-    TOPO_REQUIRE_COUNTS("v3d_recon_mesh_corner_records", num_verts, num_faces);
+    MESH_REQUIRE_COUNTS("v3d_recon_mesh_corner_records", num_verts, num_faces);
     hipLaunchKernelGGL(mesh_corner_records_kernel, dim3(nblk(3LL * num_faces)), dim3(NT), 0, ST, faces, 3LL * num_faces, (int)num_verts,
                        (unsigned long long*)keys, vals);
     return check_launch("v3d_recon_mesh_corner_records");
@@ -265,9 +222,9 @@ extern "C" int v3d_recon_mesh_corner_records(const int32_t* faces, int32_t num_f
 extern "C" int v3d_recon_mesh_vertex_normals(const float* verts, int32_t num_verts, const int32_t* faces, int32_t num_faces, const int32_t* ranges,
                                              const int32_t* corners, float* normals, v3d_stream_t stream) {
     RECON_REQUIRE(verts && faces && ranges && corners && normals, "v3d_recon_mesh_vertex_normals: null argument");
-    TOPO_REQUIRE_COUNTS("v3d_recon_mesh_vertex_normals", num_verts, num_faces);
-    hipLaunchKernelGGL(mesh_vertex_normals_kernel, dim3(nblk(num_verts)), dim3(NT), 0, ST, verts, (int)num_verts, faces, (int)num_faces, ranges, corners,
-                       normals);
+    MESH_REQUIRE_COUNTS("v3d_recon_mesh_vertex_normals", num_verts, num_faces);
+    const Lists L{faces, ranges, corners, (int)num_faces, (int)num_verts};
+    hipLaunchKernelGGL(mesh_vertex_normals_kernel, dim3(nblk(num_verts)), dim3(NT), 0, ST, verts, L, normals);
     return check_launch("v3d_recon_mesh_vertex_normals");
 }
 
@@ -275,16 +232,16 @@ extern "C" int v3d_recon_mesh_label_round(const int32_t* faces, int32_t num_face
                                           const int32_t* labels_in, int32_t* labels_out, int32_t* changed, v3d_stream_t stream) {
     RECON_REQUIRE(faces && ranges && corners && labels_in && labels_out && changed, "v3d_recon_mesh_label_round: null argument");
     RECON_REQUIRE(labels_in != labels_out, "v3d_recon_mesh_label_round: labels_in and labels_out must be two buffers");
-    TOPO_REQUIRE_COUNTS("v3d_recon_mesh_label_round", num_verts, num_faces);
-    hipLaunchKernelGGL(mesh_label_round_kernel, dim3(nblk(num_verts)), dim3(NT), 0, ST, faces, (int)num_faces, ranges, corners, (int)num_verts, labels_in,
-                       labels_out, changed);
+    MESH_REQUIRE_COUNTS("v3d_recon_mesh_label_round", num_verts, num_faces);
+    const Lists L{faces, ranges, corners, (int)num_faces, (int)num_verts};
+    hipLaunchKernelGGL(mesh_label_round_kernel, dim3(nblk(num_verts)), dim3(NT), 0, ST, L, labels_in, labels_out, changed);
     return check_launch("v3d_recon_mesh_label_round");
 }
 
 extern "C" int v3d_recon_mesh_face_labels(const int32_t* faces, int32_t num_faces, const int32_t* labels, int32_t num_verts, uint64_t* keys,
                                           uint32_t* vals, v3d_stream_t stream) {
     RECON_REQUIRE(faces && labels && keys && vals, "v3d_recon_mesh_face_labels: null argument");
-    TOPO_REQUIRE_COUNTS("v3d_recon_mesh_face_labels", num_verts, num_faces);
+    MESH_REQUIRE_COUNTS("v3d_recon_mesh_face_labels", num_verts, num_faces);
     hipLaunchKernelGGL(mesh_face_labels_kernel, dim3(nblk(num_faces)), dim3(NT), 0, ST, faces, (int)num_faces, labels, (int)num_verts,
                        (unsigned long long*)keys, vals);
     return check_launch("v3d_recon_mesh_face_labels");
@@ -293,10 +250,10 @@ extern "C" int v3d_recon_mesh_face_labels(const int32_t* faces, int32_t num_face
 extern "C" int v3d_recon_mesh_keep_flags(const int32_t* faces, int32_t num_faces, const int32_t* ranges, const int32_t* corners, int32_t num_verts,
                                          const int32_t* labels, const int32_t* keep_root, int32_t* keep_face, int32_t* keep_vert, v3d_stream_t stream) {
     RECON_REQUIRE(faces && ranges && corners && labels && keep_root && keep_face && keep_vert, "v3d_recon_mesh_keep_flags: null argument");
-    TOPO_REQUIRE_COUNTS("v3d_recon_mesh_keep_flags", num_verts, num_faces);
+    MESH_REQUIRE_COUNTS("v3d_recon_mesh_keep_flags", num_verts, num_faces);
     const long long n = num_faces > num_verts ? num_faces : num_verts;
-    hipLaunchKernelGGL(mesh_keep_flags_kernel, dim3(nblk(n)), dim3(NT), 0, ST, faces, (int)num_faces, ranges, corners, (int)num_verts, labels, keep_root,
-                       keep_face, keep_vert);
+    const Lists L{faces, ranges, corners, (int)num_faces, (int)num_verts};
+    hipLaunchKernelGGL(mesh_keep_flags_kernel, dim3(nblk(n)), dim3(NT), 0, ST, L, labels, keep_root, keep_face, keep_vert);
     return check_launch("v3d_recon_mesh_keep_flags");
 }
 
@@ -304,7 +261,7 @@ extern "C" int v3d_recon_mesh_compact_faces(const int32_t* faces, int32_t num_fa
                                             const int32_t* keep_vert, const int32_t* vert_off, int32_t num_faces_out, int32_t num_verts_out,
                                             int32_t* faces_out, v3d_stream_t stream) {
     RECON_REQUIRE(faces && keep_face && face_off && keep_vert && vert_off && faces_out, "v3d_recon_mesh_compact_faces: null argument");
-    TOPO_REQUIRE_COUNTS("v3d_recon_mesh_compact_faces", num_verts, num_faces);
+    MESH_REQUIRE_COUNTS("v3d_recon_mesh_compact_faces", num_verts, num_faces);
     RECON_REQUIRE(num_faces_out > 0 && num_faces_out <= num_faces && num_verts_out > 0 && num_verts_out <= num_verts,
                   "v3d_recon_mesh_compact_faces: %d faces and %d vertices out of %d and %d", (int)num_faces_out, (int)num_verts_out, (int)num_faces,
                   (int)num_verts);
@@ -316,8 +273,9 @@ extern "C" int v3d_recon_mesh_compact_faces(const int32_t* faces, int32_t num_fa
 extern "C" int v3d_recon_mesh_boundary_flags(const int32_t* faces, int32_t num_faces, const int32_t* ranges, const int32_t* corners, int32_t num_verts,
                                              int32_t* flags, v3d_stream_t stream) {
     RECON_REQUIRE(faces && ranges && corners && flags, "v3d_recon_mesh_boundary_flags: null argument");
-    TOPO_REQUIRE_COUNTS("v3d_recon_mesh_boundary_flags", num_verts, num_faces);
-    hipLaunchKernelGGL(mesh_boundary_flags_kernel, dim3(nblk(num_verts)), dim3(NT), 0, ST, faces, (int)num_faces, ranges, corners, (int)num_verts, flags);
+    MESH_REQUIRE_COUNTS("v3d_recon_mesh_boundary_flags", num_verts, num_faces);
+    const Lists L{faces, ranges, corners, (int)num_faces, (int)num_verts};
+    hipLaunchKernelGGL(mesh_boundary_flags_kernel, dim3(nblk(num_verts)), dim3(NT), 0, ST, L, flags);
     return check_launch("v3d_recon_mesh_boundary_flags");
 }
 
@@ -325,9 +283,9 @@ extern "C" int v3d_recon_mesh_smooth_pass(const float* verts_in, int32_t num_ver
                                           const int32_t* corners, const int32_t* pinned, float factor, float* verts_out, v3d_stream_t stream) {
     RECON_REQUIRE(verts_in && faces && ranges && corners && verts_out, "v3d_recon_mesh_smooth_pass: null argument");
     RECON_REQUIRE(verts_in != verts_out, "v3d_recon_mesh_smooth_pass: verts_in and verts_out must be two buffers");
-    TOPO_REQUIRE_COUNTS("v3d_recon_mesh_smooth_pass", num_verts, num_faces);
+    MESH_REQUIRE_COUNTS("v3d_recon_mesh_smooth_pass", num_verts, num_faces);
     RECON_REQUIRE(isfinite(factor), "v3d_recon_mesh_smooth_pass: factor %g is not finite", (double)factor);
-    hipLaunchKernelGGL(mesh_smooth_pass_kernel, dim3(nblk(num_verts)), dim3(NT), 0, ST, verts_in, (int)num_verts, faces, (int)num_faces, ranges, corners,
-                       pinned, factor, verts_out);
+    const Lists L{faces, ranges, corners, (int)num_faces, (int)num_verts};
+    hipLaunchKernelGGL(mesh_smooth_pass_kernel, dim3(nblk(num_verts)), dim3(NT), 0, ST, verts_in, L, pinned, factor, verts_out);
     return check_launch("v3d_recon_mesh_smooth_pass");
 }

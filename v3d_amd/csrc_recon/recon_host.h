@@ -1,6 +1,6 @@
-// Shared by the sources of libv3d_recon.so (geom.hip, meshrast.hip, meshshade.hip, meshtopo.hip): the host helpers behind every entry (return codes, the one error string
-// behind v3d_recon_last_error(), the launch check) and the two launch-shape constants that kernels and launches of these files agree on
-// (TILE, NT).  No device functions.
+// Shared by every source of libv3d_recon.so (all of csrc_recon/*.hip, directly or through bvh_walk.h and mesh_lists.h): the host helpers
+// behind every entry (return codes, the one error string behind v3d_recon_last_error(), the launch check) and the two launch-shape constants
+// that kernels and launches of these files agree on (TILE, NT).  No device functions.
 #ifndef V3D_RECON_HOST_H
 #define V3D_RECON_HOST_H
 #include <hip/hip_runtime.h>

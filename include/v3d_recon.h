@@ -720,6 +720,69 @@ int v3d_recon_remesh_project(const int32_t* hit_face, const float* hit_uv, const
                              const int32_t* src_faces, int32_t src_num_faces, float* verts, float* colors, int32_t num_verts,
                              v3d_stream_t stream);
 
+/* ---- Mesh check (v3d_amd/csrc_recon/meshcheck.hip; host side: v3d_amd/recon/mesh_check.py) --------------------------------------------------
+ * "Is this mesh sound": which pairs of faces pass through each other, on the tree of "Mesh BVH and normal bake" (THE NODES; the tree
+ * arguments come in the order of v3d_recon_bvh_closest_hit, and there is no query array: the queries are the mesh's own faces), and how many
+ * faces meet at every edge and which way they run, on the corner lists of "Mesh topology".
+ *   pairs:   v3d_recon_bvh_self_count -> v3d_gs_scan of n_up -> v3d_recon_bvh_self_emit -> sort on f << 32 | g (v3d_gs_radix_sort_pairs)
+ *   census:  the corner lists -> v3d_recon_mesh_edge_census;  v3d_recon_mesh_vertex_census
+ * No atomics.  All arithmetic is float, and nothing is contracted: every product is rounded on its own.
+ *
+ * THE PAIR RULE.  Faces f != g are a pair when (a), (b), (c) and (d) hold.  The rule is always evaluated with the face of the lower index as
+ * A = (a0, a1, a2) and the other as B = (b0, b1, b2), so (f, g) and (g, f) are one decision.
+ *   (a) Both faces are present (every index in 0 .. V-1) and both have area: not |e1 x e2|^2 == 0, taken as in v3d_recon_bvh_closest_point
+ *       (in every component of e1 x e2 the two products, each rounded on its own, are equal), e1 = v1 - v0, e2 = v2 - v0.
+ *   (b) Their boxes meet.  A face's box is lo = min, hi = max of its three vertices per axis; two boxes meet when lo_A <= hi_B and
+ *       lo_B <= hi_A on all three axes (closed, no slack: a crossing point lies in both exact boxes).
+ *   (c) s = the number of (i, j) with A's index i equal to B's index j.  s >= 2 (an edge in common, or the same three vertices): never a
+ *       pair.  s == 1, the shared vertex at corner ka of A and kb of B: two tests, in this order: A's edge from corner ka + 1 to ka + 2
+ *       (mod 3; the edge opposite the shared vertex) against B, then B's edge from kb + 1 to kb + 2 against A.  s == 0: six tests, in this
+ *       order: A's edges a0 a1, a1 a2, a2 a0 against B, then B's edges b0 b1, b1 b2, b2 b0 against A.  A pair when any test holds.
+ *   (d) THE EDGE (p, q) AGAINST THE TRIANGLE (a, b, c):  e1 = b - a, e2 = c - a, n = e1 x e2 (a component is u_y w_z - u_z w_y, and so on),
+ *       dp = n . (p - a), dq = n . (q - a), a dot product being (x x' + y y') + z z'.  The endpoints lie strictly on opposite sides:
+ *       (dp > 0 and dq < 0) or (dp < 0 and dq > 0);  else the test fails.  Then d = q - p and
+ *       ta = d . ((b - p) x (c - p)),  tb = d . ((c - p) x (a - p)),  tc = d . ((a - p) x (b - p)).
+ *       ta + tb + tc = d . n in exact arithmetic, and the crossing point's barycentrics are ta, tb, tc over d . n, which has the sign of -dp:
+ *       the test holds when dp > 0 and ta <= 0, tb <= 0, tc <= 0, or dp < 0 and ta >= 0, tb >= 0, tc >= 0.  No quotient is formed.
+ * Not decided by this rule: two faces that overlap in one plane (no endpoint is strictly off the plane), and two faces with an edge in common
+ * however sharply they are folded onto each other. */
+
+/* One thread per face, 64 to a block, a stack of V3D_RECON_BVH_STACK nodes per face in LDS.  Thread i takes face f = order[i] (the i-th leaf;
+ * order must hold every face once, as v3d_recon_bvh_build_nodes leaves it;  a thread whose order[i] lies outside 0 .. F-1 writes nothing).
+ * The walk starts at the root, visits every node whose box meets f's box by (b), descends the left child and pushes the right, and at a
+ * leaf with face g != f decides THE PAIR RULE;  it is bounded by the node count and drops a push past the stack.
+ * n_all [F]: the partners of f of either index order;  n_up [F]: the partners g > f.  A face that fails (a) has 0 and 0. */
+int v3d_recon_bvh_self_count(const int32_t* left, const int32_t* right, const uint32_t* order, const float* lo, const float* hi, const float* verts,
+                             int32_t num_verts, const int32_t* faces, int32_t num_faces, int32_t* n_all, int32_t* n_up, v3d_stream_t stream);
+
+/* The same walk.  offsets [F + 1]: the exclusive scan of n_up with its total (v3d_gs_scan);  pairs [num_pairs][2], num_pairs >= 1.  The j-th
+ * partner g > f that the walk meets is written as pairs[offsets[f] + j] = (f, g) while offsets[f] + j < min(offsets[f + 1], num_pairs):
+ * nothing is written past the buffer or into another face's rows, whatever offsets holds.  The rows come grouped by f in ascending f, and
+ * within one f in the order of the walk. */
+int v3d_recon_bvh_self_emit(const int32_t* left, const int32_t* right, const uint32_t* order, const float* lo, const float* hi, const float* verts,
+                            int32_t num_verts, const int32_t* faces, int32_t num_faces, const int32_t* offsets, int32_t num_pairs, int32_t* pairs,
+                            v3d_stream_t stream);
+
+/* THE CENSUS.  A face is COUNTED when it is present and its three indices differ.  An entry of v's list (v3d_recon_mesh_corner_records) at
+ * place k of a counted face (i0, i1, i2) has the next neighbour i_(k+1) and the previous neighbour i_(k+2) (mod 3): the face runs
+ * v -> next and previous -> v.
+ * One thread per corner c = 3 f + k, the half-edge i_k -> i_(k+1) of face f.  It walks i_k's list:  same [3F]: the entries of counted faces
+ * whose next neighbour is i_(k+1), the corner's own entry included (the faces that run i_k -> i_(k+1));  opposite [3F]: those whose previous
+ * neighbour is i_(k+1) (the faces that run i_(k+1) -> i_k).  A corner of a face that is not counted: -1 and -1. */
+int v3d_recon_mesh_edge_census(const int32_t* faces, int32_t num_faces, const int32_t* ranges, const int32_t* corners, int32_t num_verts,
+                               int32_t* same, int32_t* opposite, v3d_stream_t stream);
+
+/* One thread per vertex v.  For every neighbour u of v in a counted entry of v's list, out = the counted entries whose next neighbour is u and
+ * in = those whose previous neighbour is u (same and opposite of the half-edge v -> u).  flags [V], the OR over these edges of
+ *   1: out + in == 1 (an open edge);   2: out + in >= 3 (a non-manifold edge);
+ *   4: (out == 2 and in == 0) or (in == 2 and out == 0) (two faces that run the same way: the winding is inconsistent);
+ * and, only where none of these is set and v's list has at least one present face (counted or not),
+ *   8: v's star is not one closed fan by the rule of v3d_recon_mesh_decim_propose (two cones that meet at a point; also a face that names
+ *      v twice).
+ * 0 for a vertex without faces. */
+int v3d_recon_mesh_vertex_census(const int32_t* faces, int32_t num_faces, const int32_t* ranges, const int32_t* corners, int32_t num_verts,
+                                 int32_t* flags, v3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -117,6 +117,11 @@ SIGNATURES = {
     "v3d_recon_remesh_flip_apply": (c_i32, [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "v3d_recon_remesh_relax": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_f32, c_vp, c_vp]),
     "v3d_recon_remesh_project": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_i32, c_vp]),
+    # mesh check (csrc_recon/meshcheck.hip, v3d_amd/recon/mesh_check.py)
+    "v3d_recon_bvh_self_count": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp]),
+    "v3d_recon_bvh_self_emit": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp]),
+    "v3d_recon_mesh_edge_census": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp]),
+    "v3d_recon_mesh_vertex_census": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp]),
 }
 
 _lib = None

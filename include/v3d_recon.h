@@ -783,6 +783,114 @@ int v3d_recon_mesh_edge_census(const int32_t* faces, int32_t num_faces, const in
 int v3d_recon_mesh_vertex_census(const int32_t* faces, int32_t num_faces, const int32_t* ranges, const int32_t* corners, int32_t num_verts,
                                  int32_t* flags, v3d_stream_t stream);
 
+/* ---- Mesh repair (v3d_amd/csrc_recon/meshrepair.hip; host side: v3d_amd/recon/mesh_repair.py) ---------------------------------------------
+ * Acts on what "Mesh check" reports and keeps every triangle it has no reason to touch.  Five passes, each an entry or a few, each reading
+ * the corner lists of "Mesh topology" and the outputs of THE CENSUS and of the self-pair walk as they are:
+ *   weld:    weld_keys -> sort on z (32 bits), then on x << 32 | y (64 bits) -> weld_heads -> v3d_gs_scan -> weld_first -> weld_remap ->
+ *            remap_faces
+ *   drop:    the corner lists -> drop_flags -> scan of the kept -> v3d_recon_mesh_compact_faces
+ *   orient:  the census -> labels = 2 f, then orient_round between two buffers until a round changes nothing -> orient_conflicts ->
+ *            orient_apply;  the host sums every closed patch's signed volume in float64 in face order and flips a negative patch whole
+ *   cut:     the census and the pairs -> vertex_open -> trouble -> grow (between two buffers, `grow` times) -> compaction of the rest
+ *   fill:    the census of what is left -> vertex_open -> 32 x loop_round between two buffers -> sort of the live vertices on their label ->
+ *            v3d_recon_mesh_vertex_ranges -> loop_flags -> scans of the new faces and vertices -> fill_emit
+ * (every name above with the prefix v3d_recon_repair_).  One thread per vertex, face or loop.  No atomics: every element has one owner, and
+ * the two flag words (changed, nonorient) only ever receive a 1.  Integers everywhere but in three places: coordinates are compared by value
+ * (weld), the area rule is that of THE PAIR RULE (a), and a loop's centre is a float64 sum rounded once.  Two runs are bit-equal.  A face with
+ * an index outside 0 .. V-1 is absent and nothing is read through such an index;  COUNTED is as in THE CENSUS. */
+
+/* WELD.  Two vertices are one when their three float32 coordinates are equal by value (-0.0 equals +0.0;  the host refuses a coordinate
+ * that is not finite).  One thread per vertex: keys_z [V] = the bits of z, keys_xy [V] = the bits of x << 32 | the bits of y, a coordinate
+ * equal to zero taken as bits 0;  vals [V] = v.  Two stable sorts (z, then x y) leave equal positions next to each other, indices ascending. */
+int v3d_recon_repair_weld_keys(const float* verts, int32_t num_verts, uint64_t* keys_z, uint64_t* keys_xy, uint32_t* vals, v3d_stream_t stream);
+
+/* order [V]: the sorted values.  heads [V]: 1 for i == 0 and where the position of order[i] differs by value from that of order[i - 1] (also
+ * where either index lies outside 0 .. V-1), else 0. */
+int v3d_recon_repair_weld_heads(const float* verts, int32_t num_verts, const int32_t* order, int32_t* heads, v3d_stream_t stream);
+
+/* offsets [V + 1]: the exclusive scan of heads.  first [V]: first[offsets[i]] = order[i] for every head i: the representative of group
+ * offsets[i], its smallest index.  Rows past the number of groups are not written. */
+int v3d_recon_repair_weld_first(const int32_t* order, const int32_t* heads, const int32_t* offsets, int32_t num_verts, int32_t* first,
+                                v3d_stream_t stream);
+
+/* remap [V]: remap[order[i]] = first[offsets[i + 1] - 1], the representative of i's group (the vertex itself where an index is out of range). */
+int v3d_recon_repair_weld_remap(const int32_t* order, const int32_t* offsets, const int32_t* first, int32_t num_verts, int32_t* remap,
+                                v3d_stream_t stream);
+
+/* faces_out [F][3] (two buffers): every index of a present face replaced by remap of it;  an absent face is copied. */
+int v3d_recon_repair_remap_faces(const int32_t* faces, int32_t num_faces, int32_t num_verts, const int32_t* remap, int32_t* faces_out,
+                                 v3d_stream_t stream);
+
+/* DROP.  drop [F], one thread per face, the OR of  1: absent (and nothing else);  2: present and not counted (an index twice);  4: present
+ * and without area by THE PAIR RULE (a), e1 = v1 - v0, e2 = v2 - v0;  8: counted, and a present face of a lower index holds the same three
+ * indices in any order (the thread walks the list of its smallest index).  A face is dropped when its word is not 0. */
+int v3d_recon_repair_drop_flags(const float* verts, int32_t num_verts, const int32_t* faces, int32_t num_faces, const int32_t* ranges,
+                                const int32_t* corners, int32_t* drop, v3d_stream_t stream);
+
+/* ORIENT.  same, opposite [3F] of v3d_recon_mesh_edge_census on the same faces.  The counted faces f and g are ADJACENT across half-edge k of
+ * f, i_k -> i_(k+1), when same + opposite == 2 there;  rel = 1 when same == 2 (both run the same way) else 0;  g is the other counted entry
+ * of i_k's list whose next (rel = 1) or previous (rel = 0) neighbour is i_(k+1).  One round, one thread per face, between two buffers:
+ * labels_out[f] = min(labels_in[f], min over adjacent g of (labels_in[g] XOR rel)), from labels = 2 f.  A thread whose label changed stores 1
+ * to changed [1], which the caller cleared.  Plain propagation: the fixed point comes within the face graph's diameter + 1 rounds, and F + 8
+ * rounds without one mean broken lists.  At the fixed point label >> 1 is the smallest face of the patch and label & 1 says "flip me
+ * relative to that face". */
+int v3d_recon_repair_orient_round(const int32_t* faces, int32_t num_faces, const int32_t* ranges, const int32_t* corners, int32_t num_verts,
+                                  const int32_t* same, const int32_t* opposite, const int32_t* labels_in, int32_t* labels_out, int32_t* changed,
+                                  v3d_stream_t stream);
+
+/* nonorient [F], cleared by the caller: nonorient[label[f] >> 1] = 1 for every adjacent pair f, g with equal roots and
+ * (label[f] XOR label[g]) & 1 != rel.  Such a patch cannot be given one winding. */
+int v3d_recon_repair_orient_conflicts(const int32_t* faces, int32_t num_faces, const int32_t* ranges, const int32_t* corners, int32_t num_verts,
+                                      const int32_t* same, const int32_t* opposite, const int32_t* labels, int32_t* nonorient, v3d_stream_t stream);
+
+/* faces_out [F][3] (two buffers): places 1 and 2 of face f change places when its root r = labels[f] >> 1 has nonorient[r] == 0 and
+ * (labels[f] & 1) XOR (patch_flip[r] != 0) is 1;  patch_flip [F] by root, or NULL for none.  Every other face is copied. */
+int v3d_recon_repair_orient_apply(const int32_t* faces, int32_t num_faces, const int32_t* labels, const int32_t* nonorient, const int32_t* patch_flip,
+                                  int32_t* faces_out, v3d_stream_t stream);
+
+/* CUT.  An OPEN HALF-EDGE is a corner with same == 1 and opposite == 0: u -> w of the one counted face on its edge.  One thread per vertex u
+ * over u's list:  next [V] = w when u has exactly one outgoing open half-edge u -> w, else -1;  bad [V] = 1 when flags[u] (of
+ * v3d_recon_mesh_vertex_census) has bit 2, 4 or 8, or u has two or more outgoing open half-edges, else 0. */
+int v3d_recon_repair_vertex_open(const int32_t* faces, int32_t num_faces, const int32_t* ranges, const int32_t* corners, int32_t num_verts,
+                                 const int32_t* same, const int32_t* opposite, const int32_t* flags, int32_t* bad, int32_t* next, v3d_stream_t stream);
+
+/* trouble [F] = 1 for a present face with per_face[f] > 0 (n_all of v3d_recon_bvh_self_count) or a bad vertex, else 0. */
+int v3d_recon_repair_trouble(const int32_t* faces, int32_t num_faces, int32_t num_verts, const int32_t* per_face, const int32_t* bad, int32_t* trouble,
+                             v3d_stream_t stream);
+
+/* trouble_out [F] (two buffers) = trouble_in, and 1 for every present face one of whose three lists holds a present face g with
+ * trouble_in[g] != 0. */
+int v3d_recon_repair_grow(const int32_t* faces, int32_t num_faces, const int32_t* ranges, const int32_t* corners, int32_t num_verts,
+                          const int32_t* trouble_in, int32_t* trouble_out, v3d_stream_t stream);
+
+/* FILL.  From labels = v and jump = next, or -1 where bad[v] != 0 (set by the host), 32 rounds between two buffers of:  with j = jump_in[v] in
+ * 0 .. V-1, labels_out[v] = min(labels_in[v], labels_in[j]) and jump_out[v] = jump_in[j];  else the label is copied and the jump is -1.
+ * After them a vertex is LIVE when its jump is in range (its chain of next never ends and never meets a bad vertex), and a live vertex's
+ * label is the smallest vertex its chain visits. */
+int v3d_recon_repair_loop_round(int32_t num_verts, const int32_t* labels_in, const int32_t* jump_in, int32_t* labels_out, int32_t* jump_out,
+                                v3d_stream_t stream);
+
+/* members [V]: the vertices sorted (stably) on their label, a vertex that is not live on the key V: within one label they ascend, which is
+ * the order of label << 32 | vertex.  loop_ranges [V][2]: v3d_recon_mesh_vertex_ranges of the sorted keys.  One thread per vertex x:
+ * state [V] = 0 and length [V] = 0 unless x is live and labels[x] == x;  then length = n, the rows of x's range, and state = 1 (FILLABLE) when
+ * 3 <= n <= max_hole_edges and stepping u = next[u] from u = next[x] returns to x after exactly n steps through vertices that are in range,
+ * not bad and labelled x;  else state = 2 (left: too long, or x's rows hold a chain that runs into the loop and do not close.  Such a chain
+ * whose vertices all lie below the loop's smallest is a label of its own, state 2, and the loop itself is then fillable). */
+int v3d_recon_repair_loop_flags(int32_t num_verts, const int32_t* next, const int32_t* bad, const int32_t* labels, const int32_t* jump,
+                                const int32_t* loop_ranges, const int32_t* members, int32_t max_hole_edges, int32_t* state, int32_t* length,
+                                v3d_stream_t stream);
+
+/* One thread per fillable x, serial over its loop.  face_off, vert_off [V + 1]: the exclusive scans of the loop's new faces (1 when n == 3,
+ * else n) and new vertices (0 when n == 3, else 1), so loops come in ascending x.  n == 3: the face (n2, n1, x), n1 = next[x], n2 = next[n1].
+ * n > 3: the new vertex m = V + vert_off[x] at new_verts[vert_off[x]] = per coordinate the float64 sum over the loop's members in ascending
+ * index, divided by (double)n, rounded once to float32;  new_colors likewise from colors (both NULL for none);  the faces (next[u], u, m)
+ * for the members u in ascending order.  new_faces [num_new_faces][3], new_verts, new_colors [num_new_verts][3];  a loop whose rows do not
+ * fit the buffers writes nothing. */
+int v3d_recon_repair_fill_emit(const float* verts, const float* colors, int32_t num_verts, const int32_t* next, const int32_t* loop_ranges,
+                               const int32_t* members, const int32_t* state, const int32_t* length, const int32_t* face_off, const int32_t* vert_off,
+                               int32_t num_new_faces, int32_t num_new_verts, int32_t* new_faces, float* new_verts, float* new_colors,
+                               v3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -122,6 +122,22 @@ SIGNATURES = {
     "v3d_recon_bvh_self_emit": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp]),
     "v3d_recon_mesh_edge_census": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp]),
     "v3d_recon_mesh_vertex_census": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp]),
+    # mesh repair (csrc_recon/meshrepair.hip, v3d_amd/recon/mesh_repair.py)
+    "v3d_recon_repair_weld_keys": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    "v3d_recon_repair_weld_heads": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_vp]),
+    "v3d_recon_repair_weld_first": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_vp, c_vp]),
+    "v3d_recon_repair_weld_remap": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_vp, c_vp]),
+    "v3d_recon_repair_remap_faces": (c_i32, [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    "v3d_recon_repair_drop_flags": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    "v3d_recon_repair_orient_round": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "v3d_recon_repair_orient_conflicts": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "v3d_recon_repair_orient_apply": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "v3d_recon_repair_vertex_open": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "v3d_recon_repair_trouble": (c_i32, [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    "v3d_recon_repair_grow": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp]),
+    "v3d_recon_repair_loop_round": (c_i32, [c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "v3d_recon_repair_loop_flags": (c_i32, [c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp]),
+    "v3d_recon_repair_fill_emit": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
 }
 
 _lib = None

@@ -891,6 +891,42 @@ int v3d_recon_repair_fill_emit(const float* verts, const float* colors, int32_t 
                                int32_t num_new_faces, int32_t num_new_verts, int32_t* new_faces, float* new_verts, float* new_colors,
                                v3d_stream_t stream);
 
+/* ---- Mesh alignment (v3d_amd/csrc_recon/meshalign.hip; host side: v3d_amd/recon/mesh_align.py) ---------------------------------------------
+ * The hot step of an ICP against the tree of "Mesh BVH and normal bake" (THE NODES; the tree arguments come in the order of
+ * v3d_recon_bvh_closest_hit): move every sample by a similarity, find its closest point on the tree's mesh, and reduce the weighted
+ * moments of the pairs from which the host solves the next similarity (Umeyama).  No atomics: every block writes one row of sums, a second
+ * entry adds the rows in a fixed order.  Two calls with the same arguments are bit-equal.
+ *
+ * THE BUTTERFLY: a value per lane of a wave becomes their sum on every lane by v += (v of lane ^ o) for o = 32, 16, 8, 4, 2, 1.  Both
+ * partners of a step add the same two numbers, and an IEEE sum does not depend on the order of its two operands, so every lane holds the
+ * same double after every step. */
+
+#define V3D_RECON_ALIGN_COLUMNS 20
+/* One thread per sample, 64 to a block (one wave);  the walk's stack lives in LDS as in "Mesh queries".  points [N][3], weights [N].
+ * xf [12] is read on the HOST before the call returns: a row-major 3 x 4 float matrix M = [s R | t].
+ * Per sample, in float:  p'_r = ((M_r0 x + M_r1 y) + M_r2 z) + M_r3  for the rows r = 0, 1, 2 (whether a product and the sum after it are
+ * contracted into one fused operation is the compiler's choice).  The closest point of the tree's mesh to p' is that of
+ * v3d_recon_bvh_closest_point with this max_dist (closed;  +inf allowed;  NaN or a negative value is refused), with exactly its rules, ties
+ * and misses;  a p' with a coordinate that is not finite is a miss (a sample with a coordinate that is not finite gives such a p').
+ * q = a + u e1 + v e2 of the face found, b itself where u == 1 and c itself where v == 1, as THE CLOSEST POINT OF A TRIANGLE forms it.
+ * Every sample writes  moved [N][3] = p',  closest [N][3] = q,  dist [N],  face [N],  uv [N][2];  a miss writes q = NaN NaN NaN, +inf, -1
+ * and 0 0.  None of these depends on the weight.
+ * A sample is VALID when the three coordinates of p' are finite and its weight is finite and >= 0.  It COUNTS when it is valid and not a
+ * miss.  Every block writes one row of partials [ceil(N / 64)][20] in double.  Every term is formed in double from the floats above, each
+ * operation rounded on its own (no contraction), products from the left:  (w q_i) p'_j,  w ((x x + y y) + z z),  w (dist dist).  A sample
+ * that does not count, and a lane past N, adds exact zeros.  The 64 terms of a column are summed by THE BUTTERFLY.
+ *   column 0: sum w          1-3: sum w p'         4-6: sum w q          7-15: sum w q_i p'_j at 7 + 3 i + j
+ *   16: sum w |p'|^2         17: sum w dist^2      18: the samples that count
+ *   19: sum w over all valid samples, counted or not */
+int v3d_recon_align_correspond(const float* points, const float* weights, int32_t num_points, const float* xf, float max_dist, const int32_t* left,
+                               const int32_t* right, const uint32_t* order, const float* lo, const float* hi, const float* verts, int32_t num_verts,
+                               const int32_t* faces, int32_t num_faces, float* moved, float* closest, float* dist, int32_t* face, float* uv,
+                               double* partials, v3d_stream_t stream);
+
+/* One block of 64 threads.  partials [num_rows][20], num_rows >= 1.  Lane l adds the rows l, l + 64, ... in increasing order, column by
+ * column, from 0.0;  THE BUTTERFLY over the lanes then gives sums [20]. */
+int v3d_recon_align_reduce(const double* partials, int32_t num_rows, double* sums, v3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

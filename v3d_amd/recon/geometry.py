@@ -138,6 +138,10 @@ SIGNATURES = {
     "v3d_recon_repair_loop_round": (c_i32, [c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "v3d_recon_repair_loop_flags": (c_i32, [c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp]),
     "v3d_recon_repair_fill_emit": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    # mesh alignment (csrc_recon/meshalign.hip, v3d_amd/recon/mesh_align.py)
+    "v3d_recon_align_correspond": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp,
+                                           c_vp, c_vp, c_vp]),
+    "v3d_recon_align_reduce": (c_i32, [c_vp, c_i32, c_vp, c_vp]),
 }
 
 _lib = None

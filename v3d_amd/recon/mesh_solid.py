@@ -116,14 +116,20 @@ def signed_distances(bvh: MeshBVH, points, beta: float = DEFAULT_BETA, max_dist:
     return {"dist": torch.where(w >= 0.5, -dist, dist), "face": face, "uv": uv, "w": w}
 
 
-def voxel_centres(resolution: int, bound: float, device="cuda") -> torch.Tensor:
-    """[N^3, 3] float32 in linear voxel order (iz N + iy) N + ix: the very floats v3d_recon_sdf_grid forms, fmaf(i + 0.5, voxel, -bound) with
+def voxel_axis(resolution: int, bound: float, device="cuda") -> torch.Tensor:
+    """[N] float32: the voxel centres along one axis, the very floats v3d_recon_sdf_grid forms, fmaf(i + 0.5, voxel, -bound) with
     voxel = 2 bound / N in float.  Formed in double, where the product and the sum are exact, and rounded to float once."""
     N = int(resolution)
     b = torch.tensor(float(bound), dtype=torch.float32)
     voxel = 2.0 * b / torch.tensor(float(N), dtype=torch.float32)
-    c = ((torch.arange(N, dtype=torch.float64) + 0.5) * voxel.double() - b.double()).float().to(device)
-    zz, yy, xx = torch.meshgrid(c, c, c, indexing="ij")
+    return ((torch.arange(N, dtype=torch.float64) + 0.5) * voxel.double() - b.double()).float().to(device)
+
+
+def voxel_centres(resolution: int, bound: float, device="cuda", layers=None) -> torch.Tensor:
+    """[N^3, 3] float32 in linear voxel order (iz N + iy) N + ix, every coordinate from voxel_axis.  layers = (z0, z1): only the voxels of
+    the z layers z0 .. z1-1, [(z1 - z0) N^2, 3], the same floats in the same order."""
+    c = voxel_axis(resolution, bound, device)
+    zz, yy, xx = torch.meshgrid(c if layers is None else c[layers[0]:layers[1]], c, c, indexing="ij")
     return torch.stack([xx, yy, zz], -1).reshape(-1, 3).contiguous()
 
 
